@@ -14,6 +14,12 @@ Contract (driver):
 One rank per GPU; warmup untimed; exactly K timed steps bracketed by
 barrier + torch.cuda.synchronize; MAX time over ranks; rank 0 prints one
 JSON line.
+
+A plain run does only what the headline figure needs. --full adds the
+side measurements (the gpu_busy sysfs sampler that runs alongside the
+timed region). --dump-outputs DIR writes what the last timed step
+produced, as float32/float64 .npy files, so two builds can be compared
+output for output (inputs are seeded: same arguments, same frames).
 """
 
 import argparse
@@ -27,6 +33,38 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
 
 BASELINE_FPS = 60.0  # reference headline: >= 60 fps at 1920x1080
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # cap on everything --dump-outputs writes
+
+
+def dump_outputs(out_dir, kept, tag="", budget=DUMP_BUDGET_BYTES):
+    """Write one frame's encoded stripes (what a caller of the pipeline
+    receives) as .npy: `bitstream` = every stripe's payload bytes
+    concatenated in emit order (float32, one value per byte), `stripes` =
+    one row per stripe [y, byte offset, byte size] (float64), `frame_id`.
+    A bitstream past `budget` bytes of output is cut to a fixed seeded
+    sample of its bytes (`bitstream_index` holds the sampled positions)."""
+    frame_id, stripes = kept
+    os.makedirs(out_dir, exist_ok=True)
+    table = np.zeros((len(stripes), 3), dtype=np.float64)
+    off = 0
+    for i, (y, payload) in enumerate(stripes):
+        table[i] = (y, off, len(payload))
+        off += len(payload)
+    raw = np.frombuffer(b"".join(p_ for _, p_ in stripes), dtype=np.uint8)
+    limit = max(0, budget - table.nbytes - 4096) // 4
+    if raw.size > limit:
+        # index (float64) + values (float32) share the budget
+        n = (limit * 4) // 12
+        idx = np.sort(np.random.default_rng(0).choice(
+            raw.size, size=n, replace=False))
+        np.save(os.path.join(out_dir, f"bitstream_index{tag}.npy"),
+                idx.astype(np.float64))
+        raw = raw[idx]
+    np.save(os.path.join(out_dir, f"bitstream{tag}.npy"),
+            raw.astype(np.float32))
+    np.save(os.path.join(out_dir, f"stripes{tag}.npy"), table)
+    np.save(os.path.join(out_dir, f"frame_id{tag}.npy"),
+            np.array([frame_id], dtype=np.float64))
 
 
 def run_e2e(args):
@@ -186,7 +224,20 @@ def main():
                          "frame's stripe bands split across GPUs (strong "
                          "scaling of single-stream latency — stripes are "
                          "independent bitstreams, the multi-GPU seam)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements a plain run "
+                         "leaves out (gpu_busy sysfs sampling alongside "
+                         "the timed region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the encoded stripes "
+                         "of the last timed frame as DIR/<name>.npy "
+                         "(float32/float64, at most 64 MB in all); inputs "
+                         "are seeded, so equal arguments give equal inputs")
     args = ap.parse_args()
+    if args.dump_outputs and args.mode == "e2e":
+        ap.error("--dump-outputs is not available with --mode e2e")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.width is None or args.height is None:
         if args.encoder.startswith("hevc"):
             args.width, args.height = 3840, 2160
@@ -322,7 +373,7 @@ def main():
                 break
 
         def __enter__(self):
-            if self.path is None or not use_gpu:
+            if self.path is None or not use_gpu or not args.full:
                 return self
             import threading as _t
 
@@ -357,6 +408,9 @@ def main():
     sync()
     busy = BusySampler(local_rank if use_gpu else -1)
     busy.__enter__()
+    # the last timed step keeps a copy of the stripes it emits (with one
+    # frame in flight that is the flush at the end of the timed region)
+    dump = args.dump_outputs is not None
     lat_ms = []
     total_bytes = 0
     if n_sess == 1:
@@ -369,6 +423,8 @@ def main():
         next_fid = 1 + max(1, args.warmup - 1)
         t0 = time.perf_counter()
         for i in range(args.steps):
+            if dump and i == args.steps - 1:
+                pipe.keep_stripes = True
             starts[next_fid] = time.perf_counter()
             next_fid += 1
             nbytes, _ = pipe.encode(frames[i % n_src], False)
@@ -394,6 +450,8 @@ def main():
         def run_one(si):
             p_ = pipes[si]
             for i in range(args.steps):
+                if dump and i == args.steps - 1:
+                    p_.keep_stripes = True
                 ts = time.perf_counter()
                 b, _ = p_.encode(frames[(i + si) % n_src], False)
                 per[si].append((time.perf_counter() - ts) * 1e3)
@@ -414,6 +472,13 @@ def main():
             lat_ms.extend(q)
         total_bytes = sum(nb)
 
+    if dump:
+        for si, p_ in enumerate(pipes):
+            tag = "" if n_sess == 1 else f"_s{si}"
+            if distributed:
+                tag += f"_r{rank}"
+            dump_outputs(args.dump_outputs, p_.kept_stripes(), tag,
+                         DUMP_BUDGET_BYTES // (n_sess * world))
 
     if not lat_ms:
         lat_ms = [0.0]

@@ -574,6 +574,20 @@ PYBIND11_MODULE(_native, m) {
     long last_frame_id = -1;   // frame whose stripes the last call emitted
     void* d_boundary = nullptr;
     size_t boundary_cap = 0;
+    // opt-in copy of the newest emitted frame's stripes (y, payload), so a
+    // caller can inspect what the pipeline produced; off on the timed path
+    bool keep_stripes = false;
+    long kept_frame_id = -1;
+    std::vector<std::pair<int, std::string>> kept;
+    void note(const EncodedStripe& st) {
+      if (!keep_stripes) return;
+      if (static_cast<long>(st.frame_id) != kept_frame_id) {
+        kept.clear();
+        kept_frame_id = st.frame_id;
+      }
+      kept.emplace_back(
+          st.y, std::string(reinterpret_cast<const char*>(st.data), st.size));
+    }
     BenchPipeline(const std::string& kind, int width, int height, int qp_,
                   int stripe, int output_mode, int gpu_id,
                   int pipeline_depth)
@@ -608,6 +622,19 @@ PYBIND11_MODULE(_native, m) {
       .def_property_readonly("pipeline",
                              [](BenchPipeline& b) { return b.p->name(); })
       .def_readonly("last_frame_id", &BenchPipeline::last_frame_id)
+      .def_readwrite("keep_stripes", &BenchPipeline::keep_stripes,
+                     "When true, encode()/flush() keep a copy of the newest "
+                     "emitted frame's stripes for kept_stripes().")
+      .def(
+          "kept_stripes",
+          [](BenchPipeline& b) {
+            py::list out;
+            for (auto& s : b.kept)
+              out.append(py::make_tuple(s.first, py::bytes(s.second)));
+            return py::make_tuple(b.kept_frame_id, out);
+          },
+          "(frame_id, [(y, payload bytes), ...]) of the newest frame "
+          "emitted while keep_stripes was set.")
       .def(
           "boundary_dev",
           [](BenchPipeline& b, int rows) {
@@ -666,6 +693,7 @@ PYBIND11_MODULE(_native, m) {
                 total += st.size;
                 ++stripes;
                 done = st.frame_id;
+                b.note(st);
               });
             }
             b.last_frame_id = done;
@@ -706,6 +734,7 @@ PYBIND11_MODULE(_native, m) {
                 total += st.size;
                 ++stripes;
                 done = st.frame_id;
+                b.note(st);
               });
               b.last_frame_id = done;
             }

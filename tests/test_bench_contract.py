@@ -38,6 +38,70 @@ def test_bench_json_contract():
     assert cfg["resolution"] == "320x192"
 
 
+BENCH_CPU = [sys.executable, str(REPO / "bench.py"), "--cpu", "--steps", "3",
+             "--warmup", "1", "--width", "320", "--height", "192"]
+
+
+def _bench_dump(out_dir, *extra):
+    p = subprocess.run(BENCH_CPU + ["--dump-outputs", str(out_dir), *extra],
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-800:]
+    d = json.loads([l for l in p.stdout.strip().splitlines()
+                    if l.startswith("{")][-1])
+    import numpy as np
+    return d, {f.stem: np.load(f) for f in sorted(out_dir.glob("*.npy"))}
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes the last timed frame's stripes as float
+    .npy; the same arguments give the same outputs run to run, and
+    --full changes neither the result line's fields nor the outputs."""
+    import numpy as np
+    d1, a = _bench_dump(tmp_path / "a")
+    d2, b = _bench_dump(tmp_path / "b", "--full")
+    assert set(a) == set(b) == {"bitstream", "stripes", "frame_id"}
+    assert set(d1) == set(d2) and d1["steps"] == d2["steps"] == 3
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64)
+        assert np.array_equal(a[name], b[name]), name
+    # warmup encodes frames 0..1, the 3 timed steps frames 2..4
+    assert a["frame_id"].tolist() == [4.0]
+    st = a["stripes"]
+    assert st[:, 0].tolist() == [0.0, 64.0, 128.0]      # 192 rows / 64
+    assert st[:, 1].tolist() == np.concatenate(
+        [[0], np.cumsum(st[:-1, 2])]).tolist()
+    bits = a["bitstream"]
+    assert bits.size == int(st[:, 2].sum()) and bits.size > 0
+    assert bits.min() >= 0 and bits.max() <= 255
+    assert np.array_equal(bits, np.round(bits))
+    # every stripe is an Annex-B stream: starts with a start code
+    for off in st[:, 1].astype(int):
+        assert bits[off:off + 3].tolist() in ([0, 0, 1], [0, 0, 0])
+
+
+def test_bench_dump_outputs_budget(tmp_path):
+    """An output past the byte budget is cut to a fixed seeded sample
+    that fits it, with the sampled positions alongside."""
+    import numpy as np
+    sys.path.insert(0, str(REPO))
+    import bench
+    rng = np.random.default_rng(5)
+    stripes = [(y, rng.integers(0, 256, 40000, dtype=np.uint8).tobytes())
+               for y in (0, 64)]
+    budget = 100_000
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), (7, stripes), budget=budget)
+    files = sorted((tmp_path / "a").glob("*.npy"))
+    assert sum(f.stat().st_size for f in files) <= budget
+    a = {f.stem: np.load(f) for f in files}
+    idx = a["bitstream_index"].astype(int)
+    assert 0 < idx.size < 80000 and np.all(np.diff(idx) > 0)
+    raw = np.frombuffer(b"".join(p for _, p in stripes), dtype=np.uint8)
+    assert np.array_equal(a["bitstream"], raw[idx].astype(np.float32))
+    for f in files:
+        assert np.array_equal(np.load(f), np.load(tmp_path / "b" / f.name))
+
+
 node = shutil.which("node")
 
 

@@ -91,7 +91,7 @@ def test_wire_binary_handler_survives_garbage():
                 pass  # rejecting is fine; raising odd errors is not
 
 
-def test_streaming_text_verbs_survive_garbage():
+def test_streaming_text_verbs_survive_garbage(sock_dir):
     """The streaming service's own control verbs (seats, gamepad remap,
     settings, acks) must shrug off malformed input from a hostile
     client without raising."""
@@ -110,7 +110,7 @@ def test_streaming_text_verbs_survive_garbage():
     import selkies_amd.gamepad as G
 
     async def main():
-        hub = G.GamepadHub(socket_dir="/tmp/selkies_fuzz_js",
+        hub = G.GamepadHub(socket_dir=str(sock_dir),
                            prefer_uinput=False)
         bad = [
             "js,c,0", "js,c,0,!!!notb64!!!,x,y", "js,c,-1,QQ==,1,1",

@@ -48,9 +48,9 @@ def test_config_roundtrip():
     assert parsed["btn_map"][0] == G.BTN_A
 
 
-def test_socket_gamepad_roundtrip(tmp_path):
+def test_socket_gamepad_roundtrip(sock_dir):
     async def main():
-        hub = G.GamepadHub(socket_dir=str(tmp_path), prefer_uinput=False)
+        hub = G.GamepadHub(socket_dir=str(sock_dir), prefer_uinput=False)
         name = base64.b64encode(b"PadX").decode()
         await hub.handle(f"js,c,0,{name},11,4")
         assert 0 in hub.pads
@@ -80,9 +80,9 @@ def test_socket_gamepad_roundtrip(tmp_path):
     asyncio.new_event_loop().run_until_complete(main())
 
 
-def test_disconnect_removes_socket(tmp_path):
+def test_disconnect_removes_socket(sock_dir):
     async def main():
-        hub = G.GamepadHub(socket_dir=str(tmp_path), prefer_uinput=False)
+        hub = G.GamepadHub(socket_dir=str(sock_dir), prefer_uinput=False)
         await hub.handle("js,c,1")
         path = hub.pads[1].path
         import os

@@ -54,14 +54,14 @@ def shim():
     return SHIM
 
 
-def test_interposer_end_to_end(shim, tmp_path):
+def test_interposer_end_to_end(shim, sock_dir):
     async def main():
-        hub = G.GamepadHub(socket_dir=str(tmp_path), prefer_uinput=False)
+        hub = G.GamepadHub(socket_dir=str(sock_dir), prefer_uinput=False)
         name_b64 = base64.b64encode(b"Selkies X360").decode()
         await hub.handle(f"js,c,0,{name_b64},11,4")
 
         env = dict(os.environ, LD_PRELOAD=shim,
-                   SELKIES_JS_SOCKET_PATH=str(tmp_path))
+                   SELKIES_JS_SOCKET_PATH=str(sock_dir))
         proc = await asyncio.create_subprocess_exec(
             sys.executable, "-c", CHILD, env=env,
             stdout=subprocess.PIPE, stderr=subprocess.PIPE)
@@ -125,17 +125,17 @@ print(json.dumps(out))
 """
 
 
-def test_interposer_evdev_surface(shim, tmp_path):
+def test_interposer_evdev_surface(shim, sock_dir):
     """SDL/evdev-style consumption: /dev/input/event1000 stats as a char
     device, answers the EVIOC* family, and read() delivers translated
     input_event records with EV_SYN framing."""
     async def main():
-        hub = G.GamepadHub(socket_dir=str(tmp_path), prefer_uinput=False)
+        hub = G.GamepadHub(socket_dir=str(sock_dir), prefer_uinput=False)
         name_b64 = base64.b64encode(b"Selkies X360").decode()
         await hub.handle(f"js,c,0,{name_b64},11,4")
 
         env = dict(os.environ, LD_PRELOAD=shim,
-                   SELKIES_JS_SOCKET_PATH=str(tmp_path))
+                   SELKIES_JS_SOCKET_PATH=str(sock_dir))
         proc = await asyncio.create_subprocess_exec(
             sys.executable, "-c", EVDEV_CHILD, env=env,
             stdout=subprocess.PIPE, stderr=subprocess.PIPE)

@@ -171,7 +171,7 @@ send("ok");
     assert out == ["ok"]
 
 
-def test_touch_verbs_drive_socket_gamepad(tmp_path):
+def test_touch_verbs_drive_socket_gamepad(sock_dir):
     """End to end: JS touch session -> wire verbs -> GamepadHub ->
     interposer socket events."""
     verbs = run_js("""
@@ -190,7 +190,7 @@ c.detach();
     assert verbs[0].startswith("js,c,0,")
 
     async def main():
-        hub = G.GamepadHub(socket_dir=str(tmp_path), prefer_uinput=False)
+        hub = G.GamepadHub(socket_dir=str(sock_dir), prefer_uinput=False)
         await hub.handle(verbs[0])
         pad = hub.pads[0]
         reader, writer = await asyncio.open_unix_connection(pad.path)

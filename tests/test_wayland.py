@@ -13,8 +13,8 @@ from selkies_amd.wayland.compositor import Compositor
 
 
 @pytest.fixture()
-def comp(tmp_path):
-    os.environ.setdefault("XDG_RUNTIME_DIR", str(tmp_path))
+def comp(sock_dir, monkeypatch):
+    monkeypatch.setenv("XDG_RUNTIME_DIR", str(sock_dir))
     c = Compositor(f"selkies-test-{os.getpid()}", 1280, 720)
     c.start()
     yield c
@@ -144,8 +144,8 @@ def test_clipboard_app_to_compositor(comp):
         cli.close()
 
 
-def test_ensure_wayland_display_idempotent(tmp_path):
-    os.environ.setdefault("XDG_RUNTIME_DIR", str(tmp_path))
+def test_ensure_wayland_display_idempotent(sock_dir, monkeypatch):
+    monkeypatch.setenv("XDG_RUNTIME_DIR", str(sock_dir))
     name = wcomp.ensure_wayland_display(f"selkies-ew-{os.getpid()}")
     try:
         assert wcomp.get_wayland_display_name() == name
