@@ -330,9 +330,14 @@ __global__ void __launch_bounds__(1024) k_h264_cavlc_rows(
   const int seg_mbw = job.seg_mbw;
   const size_t row_base = (size_t)job.mb_row * mbw + job.mbx0;
   const int nitems = items_per_row(seg_mbw);
+  // every job owns a slot sized for the WIDEST segment (out_stride_words =
+  // items_per_row(widest) * kStageWordsPerItem): striding by this job's
+  // own item count made a narrower last segment (16 MBs in 3 -> 6, 6, 4)
+  // overlap the slots of earlier jobs
+  const int slot_items = out_stride_words / kStageWordsPerItem;
   uint32_t* row_stage =
-      stage + (size_t)blockIdx.x * nitems * kStageWordsPerItem;
-  int* row_nbits = nbits + (size_t)blockIdx.x * nitems;
+      stage + (size_t)blockIdx.x * slot_items * kStageWordsPerItem;
+  int* row_nbits = nbits + (size_t)blockIdx.x * slot_items;
   uint32_t* row_out = out + (size_t)blockIdx.x * out_stride_words;
 
   // ---- precompute per-MB info into LDS (totals, cbp, modes, mvs)

@@ -478,7 +478,30 @@ PYBIND11_MODULE(_native, m) {
       "_pipeline_encode",
       [](const std::string& kind, py::list frames, int w, int h, int qp,
          int stripe_h, int output_mode, bool dump, bool fullcolor,
-         int pipeline_depth) -> py::object {
+         int pipeline_depth, py::object encode_mask) -> py::object {
+        // optional damage mask: mask[frame][stripe] -> StripeJob.encode
+        const size_t n_stripes =
+            stripe_h > 0 ? static_cast<size_t>((h + stripe_h - 1) / stripe_h)
+                         : 0;
+        std::vector<std::vector<bool>> mask;
+        if (!encode_mask.is_none()) {
+          if (!py::isinstance<py::list>(encode_mask))
+            throw py::value_error("encode_mask must be a list of lists");
+          py::list ml = encode_mask.cast<py::list>();
+          if (ml.size() != frames.size())
+            throw py::value_error("encode_mask needs one entry per frame");
+          for (py::handle fm : ml) {
+            if (!py::isinstance<py::list>(fm))
+              throw py::value_error("encode_mask must be a list of lists");
+            py::list fl = py::reinterpret_borrow<py::list>(fm);
+            if (fl.size() != n_stripes)
+              throw py::value_error(
+                  "encode_mask entry needs one bool per stripe");
+            std::vector<bool> row;
+            for (py::handle b : fl) row.push_back(b.cast<bool>());
+            mask.push_back(std::move(row));
+          }
+        }
         CaptureSettings s;
         s.capture_width = w;
         s.capture_height = h;
@@ -529,7 +552,7 @@ PYBIND11_MODULE(_native, m) {
             StripeJob j;
             j.y0 = y;
             j.y1 = std::min(y + stripe_h, h);
-            j.encode = true;
+            j.encode = mask.empty() || mask[i][ctx.stripes.size()];
             ctx.stripes.push_back(j);
           }
           p->encode_frame(f, ctx, sink);
@@ -564,7 +587,9 @@ PYBIND11_MODULE(_native, m) {
       py::arg("qp") = 26, py::arg("stripe_h") = 64,
       py::arg("output_mode") = 1, py::arg("dump") = false,
       py::arg("fullcolor") = false, py::arg("pipeline_depth") = 1,
-      "Test hook: run frames through a named encode pipeline.");
+      py::arg("encode_mask") = py::none(),
+      "Test hook: run frames through a named encode pipeline. "
+      "encode_mask[frame][stripe] (optional) gates which stripes encode.");
 
   // ---- persistent pipeline handle for benchmarking ------------------------
   struct BenchPipeline {

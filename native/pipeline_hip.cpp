@@ -1041,6 +1041,10 @@ class HipH264Pipeline : public EncodePipeline {
 
   bool debug_dump(DebugDump& d) override {
     HIP_CHECK(hipStreamSynchronize(stream_));
+    // the cur -> ref refresh rides rows_stream_ (gated on db_stream_), and
+    // the streams are non-blocking, so the blocking copies below do not
+    // wait for it on their own
+    HIP_CHECK(hipStreamSynchronize(rows_stream_));
     d.w = w_;
     d.h = h_;
     d.ypitch = ypitch_;

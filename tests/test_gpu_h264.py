@@ -639,7 +639,10 @@ def test_gpu_deblock_recon_matches_decoder():
     # reassemble rows separately (independent bitstreams)
     rows = reassemble(out)
     ypitch = dump["ypitch"]
+    cpitch = dump["cpitch"]
     ry = np.frombuffer(dump["y"], np.uint8).reshape(-1, ypitch)
+    rcb = np.frombuffer(dump["cb"], np.uint8).reshape(-1, cpitch)
+    rcr = np.frombuffer(dump["cr"], np.uint8).reshape(-1, cpitch)
     for y0, s in rows.items():
         decoded = Decoder().decode(s)
         assert len(decoded) == n
@@ -647,6 +650,12 @@ def test_gpu_deblock_recon_matches_decoder():
         gy = ry[y0:y0 + dy.shape[0], :w]
         assert np.array_equal(dy, gy), (
             f"stripe y={y0}: decoder recon != GPU deblocked recon")
+        for name, dc, rc in (("cb", decoded[-1][1], rcb),
+                             ("cr", decoded[-1][2], rcr)):
+            assert dc.shape == (dy.shape[0] // 2, w // 2)
+            gc = rc[y0 // 2:y0 // 2 + dc.shape[0], :w // 2]
+            assert np.array_equal(dc, gc), (
+                f"stripe y={y0}: decoder {name} != GPU deblocked {name}")
 
 
 def test_gpu_fractional_scale_stream():
