@@ -2,6 +2,7 @@
 // API surface mirrors the pixelflux contract the reference control plane
 // consumes.
 #include <pybind11/functional.h>
+#include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
@@ -9,6 +10,7 @@
 #include "cpu/damage.h"
 #include "cpu/h264/cavlc.h"
 #include "cpu/h264/encoder.h"
+#include "cpu/h264/seg_plan.h"
 #include "cpu/hevc/cabac.h"
 #include "cpu/hevc/encoder.h"
 #include "cpu/opus/celt.h"
@@ -767,6 +769,23 @@ PYBIND11_MODULE(_native, m) {
           },
           py::arg("bgrx"), py::arg("idr") = false,
           "Encode one frame; returns (bitstream_bytes, stripes).");
+
+  m.def(
+      "_h264_seg_plan",
+      [](py::array_t<int> mbw, py::array_t<int> mbh,
+         py::array_t<int> override_segs) {
+        auto segs = py::vectorize([](int w, int h, int o) {
+          return h264::seg_plan(w, h, o).segs;
+        });
+        auto widest = py::vectorize([](int w, int h, int o) {
+          return h264::seg_plan(w, h, o).widest;
+        });
+        return py::make_tuple(segs(mbw, mbh, override_segs),
+                              widest(mbw, mbh, override_segs));
+      },
+      py::arg("mbw"), py::arg("mbh"), py::arg("override_segs") = 0,
+      "Slice plan of the HIP H.264 pipeline -> (slices per MB row, widest "
+      "slice in MBs); override_segs < 1 = none. Broadcasts over arrays.");
 
   m.def(
       "_cavlc_bits",

@@ -5,15 +5,8 @@
 // Byte-identical to CpuHevcPipeline (asserted by tests/test_gpu_hevc.py);
 // HIPFLUX_CPU_HEVC_ENTROPY=1 swaps the CABAC kernel for the host entropy
 // coder over D2H levels/meta to isolate rows-kernel vs entropy bugs.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
-#include <map>
-#include <cstring>
-#include <stdexcept>
-#include <vector>
 
 #include "cpu/hevc/encoder.h"       // default_slices_per_row
 #include "cpu/hevc/gpu_entropy.h"
@@ -21,66 +14,20 @@
 #include "engine.h"
 #include "hip/hevc_kernels.h"
 #include "hip/jpeg_kernels.h"       // launch_bgrx_to_planes
+#include "hip_host.h"
 #include "thread_pool.h"
 
 namespace hipflux {
 namespace {
 
-#define HIP_CHECK(expr)                                                    \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess) {                                                \
-      throw std::runtime_error(std::string("HIP error: ") +                \
-                               hipGetErrorString(_e) + " at " #expr);      \
-    }                                                                      \
-  } while (0)
-
 class HipHevcPipeline : public EncodePipeline {
  public:
   explicit HipHevcPipeline(const CaptureSettings& s)
-      : settings_(s),
-        pool_(std::min(16u,
-                       std::max(2u, std::thread::hardware_concurrency() / 2))) {
-    HIP_CHECK(hipSetDevice(std::max(0, s.gpu_id)));
-    HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    HIP_CHECK(hipStreamCreateWithFlags(&copy_stream_, hipStreamNonBlocking));
-    HIP_CHECK(hipStreamCreateWithFlags(&rows_stream_, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i)
-      HIP_CHECK(hipEventCreateWithFlags(&ev_rows_[i],
-                                        hipEventDisableTiming));
+      : settings_(s), pool_(encode_pool_threads()), dev_(s.gpu_id) {
     cpu_entropy_ = std::getenv("HIPFLUX_CPU_HEVC_ENTROPY") != nullptr;
     timing_ = std::getenv("HIPFLUX_TIMES") != nullptr;
-    for (auto& e : ev_) HIP_CHECK(hipEventCreate(&e));
-    for (int i = 0; i < 2; ++i) {
-      HIP_CHECK(hipEventCreateWithFlags(&ev_h2d_[i],
-                                        hipEventDisableTiming));
-      HIP_CHECK(hipEventCreateWithFlags(&ev_done_[i],
-                                        hipEventDisableTiming));
-    }
     stripe_h_ = std::max(16, s.stripe_height & ~15);
     alloc_for(s.capture_width, s.capture_height);
-  }
-
-  ~HipHevcPipeline() override {
-    (void)hipStreamSynchronize(stream_);
-    (void)hipStreamSynchronize(copy_stream_);
-    for (auto& kv : registered_) (void)hipHostUnregister(kv.first);
-    for (void* p : device_ptrs_)
-      if (p) (void)hipFree(p);
-    for (int i = 0; i < 2; ++i) {
-      if (h_jobs_[i]) (void)hipHostFree(h_jobs_[i]);
-      if (h_out_[i]) (void)hipHostFree(h_out_[i]);
-      if (h_counts_[i]) (void)hipHostFree(h_counts_[i]);
-      (void)hipEventDestroy(ev_h2d_[i]);
-      (void)hipEventDestroy(ev_done_[i]);
-    }
-    if (h_levels_) (void)hipHostFree(h_levels_);
-    if (h_meta_) (void)hipHostFree(h_meta_);
-    if (h_stage_) (void)hipHostFree(h_stage_);
-    (void)hipStreamDestroy(copy_stream_);
-    (void)hipStreamSynchronize(rows_stream_);
-    (void)hipStreamDestroy(rows_stream_);
-    for (int i = 0; i < 2; ++i) (void)hipEventDestroy(ev_rows_[i]);
   }
 
   struct StripeRef {
@@ -107,31 +54,14 @@ class HipHevcPipeline : public EncodePipeline {
     const int par = parity_;
 
     // ---- upload + CSC
-    const uint8_t* src = frame.data;
-    size_t frame_bytes = static_cast<size_t>(frame.stride) * frame.height;
-    auto reg_it = registered_.find(const_cast<uint8_t*>(src));
-    if (reg_it == registered_.end()) {
-      hipError_t e = hipHostRegister(const_cast<uint8_t*>(src), frame_bytes,
-                                     hipHostRegisterDefault);
-      if (e != hipSuccess) (void)hipGetLastError();
-      reg_it = registered_.emplace(const_cast<uint8_t*>(src),
-                                   e == hipSuccess).first;
-    }
-    if (!reg_it->second) {
-      if (h_stage_bytes_ < frame_bytes) {
-        if (h_stage_) (void)hipHostFree(h_stage_);
-        HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_stage_),
-                                frame_bytes, hipHostMallocDefault));
-        h_stage_bytes_ = frame_bytes;
-      }
-      std::memcpy(h_stage_, src, frame_bytes);
-      src = h_stage_;
-    }
+    const size_t frame_bytes = static_cast<size_t>(frame.stride) * frame.height;
     // frame N+1's upload/CSC/rows run on rows_stream_, concurrent with
     // frame N's CABAC on stream_ (levels/meta are parity
     // double-buffered; the recon planes have no cross-frame reader)
-    HIP_CHECK(hipMemcpyAsync(d_frame_[par], src, frame_bytes,
-                             hipMemcpyHostToDevice, rows_stream_));
+    HIP_CHECK(hipMemcpyAsync(d_frame_[par],
+                             uploader_.source(frame.data, frame_bytes),
+                             frame_bytes, hipMemcpyHostToDevice,
+                             rows_stream_));
     HIP_CHECK(hipEventRecord(ev_h2d_[par], rows_stream_));
     launch_bgrx_to_planes(d_frame_[par], w_, h_, frame.stride / 4, d_srcY_,
                           d_srcCb_, d_srcCr_, ypitch_, cpitch_, false,
@@ -176,7 +106,7 @@ class HipHevcPipeline : public EncodePipeline {
     pd.active = true;
     parity_ ^= 1;
 
-    if (timing_) HIP_CHECK(hipEventRecord(ev_[0], rows_stream_));
+    if (timing_) HIP_CHECK(hipEventRecord(ev_t_[0], rows_stream_));
     HIP_CHECK(hipMemcpyAsync(d_jobs_[par], h_jobs_[par],
                              sizeof(hevcgpu::HevcJob) * n_jobs,
                              hipMemcpyHostToDevice, rows_stream_));
@@ -194,56 +124,44 @@ class HipHevcPipeline : public EncodePipeline {
       HIP_CHECK(hipEventRecord(ev_done_[par], stream_));
       return pd;
     }
-    if (timing_) HIP_CHECK(hipEventRecord(ev_[1], stream_));
+    if (timing_) HIP_CHECK(hipEventRecord(ev_t_[1], stream_));
     hevcgpu::launch_hevc_cabac(d_levels_[par], d_meta_[par], ctbw_, n_jobs,
                                d_jobs_[par], d_out_[par], out_stride_,
                                d_counts_[par], stream_);
-    if (timing_) HIP_CHECK(hipEventRecord(ev_[2], stream_));
+    if (timing_) HIP_CHECK(hipEventRecord(ev_t_[2], stream_));
     HIP_CHECK(hipMemcpyAsync(h_counts_[par], d_counts_[par],
                              sizeof(int) * 3 * n_jobs,
                              hipMemcpyDeviceToHost, stream_));
     // adaptive compaction: copy only ~the used prefix of each job's
     // bytes (cap = 2x last frame's max count); overflowing jobs are
     // re-copied exactly at collect time
-    pd.cap = std::min(out_stride_, copy_cap_);
-    HIP_CHECK(hipMemcpy2DAsync(h_out_[par], out_stride_, d_out_[par],
-                               out_stride_, pd.cap, n_jobs,
-                               hipMemcpyDeviceToHost, stream_));
+    pd.cap = readback_.read(h_out_[par], d_out_[par], n_jobs, stream_);
     HIP_CHECK(hipEventRecord(ev_done_[par], stream_));
     return pd;
   }
 
   // Wait for a submitted frame's D2H, assemble its NALs on the pool and
-  // emit. Overflow re-copies go over copy_stream_ so they never wait on
-  // the NEXT frame's kernels queued behind us on stream_.
+  // emit.
   void collect_pending(Pending& pd, const Emit& emit) {
     if (!pd.active) return;
     pd.active = false;
     const int par = pd.par;
-    HIP_CHECK(hipEventSynchronize(ev_done_[par]));
+    ev_done_[par].sync();
     const int n_jobs = pd.n_jobs;
     if (!cpu_entropy_) {
-      int max_count = 0;
-      bool fix = false;
-      for (int j = 0; j < n_jobs; ++j) {
-        const int cnt = h_counts_[par][j * 3];
-        max_count = std::max(max_count, cnt);
-        if (cnt > out_stride_)
-          throw std::runtime_error("hevc cabac overflow");
-        if (cnt > pd.cap) {
-          HIP_CHECK(hipMemcpyAsync(
-              h_out_[par] + (size_t)j * out_stride_,
-              d_out_[par] + (size_t)j * out_stride_, cnt,
-              hipMemcpyDeviceToHost, copy_stream_));
-          fix = true;
-        }
-      }
-      if (fix) HIP_CHECK(hipStreamSynchronize(copy_stream_));
-      copy_cap_ = std::max(4096, 2 * max_count);
+      readback_.settle(
+          h_out_[par], d_out_[par], n_jobs, pd.cap,
+          [&](int j) {
+            const int cnt = h_counts_[par][j * 3];
+            if (cnt > out_stride_)
+              throw std::runtime_error("hevc cabac overflow");
+            return cnt;
+          },
+          [](int max_count) { return std::max(4096, 2 * max_count); });
       if (timing_) {
         float t_rows = 0, t_cab = 0;
-        (void)hipEventElapsedTime(&t_rows, ev_[0], ev_[1]);
-        (void)hipEventElapsedTime(&t_cab, ev_[1], ev_[2]);
+        (void)hipEventElapsedTime(&t_rows, ev_t_[0], ev_t_[1]);
+        (void)hipEventElapsedTime(&t_cab, ev_t_[1], ev_t_[2]);
         std::fprintf(stderr, "[hevc-times] rows %.2fms cabac %.2fms\n",
                      t_rows, t_cab);
       }
@@ -314,7 +232,7 @@ class HipHevcPipeline : public EncodePipeline {
     collect_pending(prev_, emit);
     prev_ = std::move(cur);
     // the caller may reuse its frame buffer once we return
-    HIP_CHECK(hipEventSynchronize(ev_h2d_[prev_.par]));
+    ev_h2d_[prev_.par].sync();
   }
 
   void flush(const Emit& emit) override { collect_pending(prev_, emit); }
@@ -358,36 +276,13 @@ class HipHevcPipeline : public EncodePipeline {
   }
 
  private:
-  template <typename T>
-  T* dalloc(size_t n) {
-    void* p = nullptr;
-    HIP_CHECK(hipMalloc(&p, n * sizeof(T)));
-    device_ptrs_.push_back(p);
-    return static_cast<T*>(p);
-  }
-
   void alloc_for(int w, int h) {
-    HIP_CHECK(hipStreamSynchronize(stream_));
     prev_ = Pending{};          // in-flight frame is gone with its buffers
     parity_ = 0;
-    for (void* p : device_ptrs_)
-      if (p) (void)hipFree(p);
-    device_ptrs_.clear();
-    for (int i = 0; i < 2; ++i) {
-      if (h_jobs_[i]) (void)hipHostFree(h_jobs_[i]);
-      if (h_out_[i]) (void)hipHostFree(h_out_[i]);
-      if (h_counts_[i]) (void)hipHostFree(h_counts_[i]);
-      h_jobs_[i] = nullptr;
-      h_out_[i] = nullptr;
-      h_counts_[i] = nullptr;
-    }
-    if (h_levels_) (void)hipHostFree(h_levels_);
-    if (h_meta_) (void)hipHostFree(h_meta_);
-    h_levels_ = nullptr;
-    h_meta_ = nullptr;
-
-    w_ = w;
-    h_ = h;
+    stream_.sync();
+    rows_stream_.sync();
+    arena_.release();
+    w_ = h_ = 0;   // until everything below succeeded: a throw retries
     ctbw_ = (w + 15) / 16;
     ctbh_ = (h + 15) / 16;
     ypitch_ = ctbw_ * 16;
@@ -395,57 +290,55 @@ class HipHevcPipeline : public EncodePipeline {
     const int ch16 = ctbh_ * 16;
 
     for (int i = 0; i < 2; ++i)
-      d_frame_[i] =
-          dalloc<uint8_t>(static_cast<size_t>(w + 64) * 4 * (h + 16));
-    d_srcY_ = dalloc<uint8_t>(static_cast<size_t>(ypitch_) * ch16);
-    d_srcCb_ = dalloc<uint8_t>(static_cast<size_t>(cpitch_) * ch16 / 2);
-    d_srcCr_ = dalloc<uint8_t>(static_cast<size_t>(cpitch_) * ch16 / 2);
-    d_curY_ = dalloc<uint8_t>(static_cast<size_t>(ypitch_) * ch16);
-    d_curCb_ = dalloc<uint8_t>(static_cast<size_t>(cpitch_) * ch16 / 2);
-    d_curCr_ = dalloc<uint8_t>(static_cast<size_t>(cpitch_) * ch16 / 2);
+      arena_.dev(d_frame_[i], static_cast<size_t>(w + 64) * 4 * (h + 16));
+    arena_.dev(d_srcY_, static_cast<size_t>(ypitch_) * ch16);
+    arena_.dev(d_srcCb_, static_cast<size_t>(cpitch_) * ch16 / 2);
+    arena_.dev(d_srcCr_, static_cast<size_t>(cpitch_) * ch16 / 2);
+    arena_.dev(d_curY_, static_cast<size_t>(ypitch_) * ch16);
+    arena_.dev(d_curCb_, static_cast<size_t>(cpitch_) * ch16 / 2);
+    arena_.dev(d_curCr_, static_cast<size_t>(cpitch_) * ch16 / 2);
 
     const size_t n_ctu = static_cast<size_t>(ctbw_) * ctbh_;
-    levels_bytes_ = n_ctu * hevcgpu::kHevcLevelsPerCtu * sizeof(int16_t);
-    meta_bytes_ = n_ctu * hevcgpu::kHevcMetaPerCtu * sizeof(int);
+    const size_t n_levels = n_ctu * hevcgpu::kHevcLevelsPerCtu;
+    const size_t n_meta = n_ctu * hevcgpu::kHevcMetaPerCtu;
+    levels_bytes_ = n_levels * sizeof(int16_t);
+    meta_bytes_ = n_meta * sizeof(int);
     for (int i = 0; i < 2; ++i) {
-      d_levels_[i] = dalloc<int16_t>(n_ctu * hevcgpu::kHevcLevelsPerCtu);
-      d_meta_[i] = dalloc<int>(n_ctu * hevcgpu::kHevcMetaPerCtu);
+      arena_.dev(d_levels_[i], n_levels);
+      arena_.dev(d_meta_[i], n_meta);
     }
 
     const int spr = hevc::default_slices_per_row(w);
-    max_jobs_ = ctbh_ * spr + 8;
+    const size_t max_jobs = static_cast<size_t>(ctbh_) * spr + 8;
     // worst-case CABAC bytes per CTU is bounded by the coefficient count
     // (384) x a handful of bypass bytes; 2 KB/CTU is a safe ceiling
     const int per = (ctbw_ + spr - 1) / spr;
     out_stride_ = per * 2048;
     for (int i = 0; i < 2; ++i) {
-      d_jobs_[i] = dalloc<hevcgpu::HevcJob>(max_jobs_);
-      d_out_[i] =
-          dalloc<uint8_t>(static_cast<size_t>(max_jobs_) * out_stride_);
-      d_counts_[i] = dalloc<int>(static_cast<size_t>(max_jobs_) * 3);
-      HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_jobs_[i]),
-                              sizeof(hevcgpu::HevcJob) * max_jobs_,
-                              hipHostMallocDefault));
-      HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_out_[i]),
-                              static_cast<size_t>(max_jobs_) * out_stride_,
-                              hipHostMallocDefault));
-      HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_counts_[i]),
-                              sizeof(int) * 3 * max_jobs_,
-                              hipHostMallocDefault));
+      arena_.dev(d_jobs_[i], max_jobs);
+      arena_.dev(d_out_[i], max_jobs * out_stride_);
+      arena_.dev(d_counts_[i], max_jobs * 3);
+      arena_.pinned(h_jobs_[i], max_jobs);
+      arena_.pinned(h_out_[i], max_jobs * out_stride_);
+      arena_.pinned(h_counts_[i], max_jobs * 3);
     }
-    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_levels_),
-                            levels_bytes_, hipHostMallocDefault));
-    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_meta_), meta_bytes_,
-                            hipHostMallocDefault));
-    copy_cap_ = out_stride_;
+    arena_.pinned(h_levels_, n_levels);
+    arena_.pinned(h_meta_, n_meta);
+    readback_.reset(out_stride_, out_stride_);   // first frame: full copy
+    w_ = w;
+    h_ = h;
   }
 
   CaptureSettings settings_;
   ThreadPool pool_;
-  hipStream_t stream_{}, copy_stream_{}, rows_stream_{};
-  hipEvent_t ev_[4] = {};
-  hipEvent_t ev_h2d_[2] = {}, ev_done_[2] = {};
-  hipEvent_t ev_rows_[2] = {};
+  UseDevice dev_;
+  Arena arena_;
+  FrameUploader uploader_;
+  Stream stream_, rows_stream_;
+  Event ev_t_[3] = {Event(hipEventDefault), Event(hipEventDefault),
+                    Event(hipEventDefault)};   // HIPFLUX_TIMES marks
+  Event ev_h2d_[2], ev_done_[2], ev_rows_[2];
+  CompactReadback<uint8_t> readback_;   // CABAC bytes per slice
   bool cpu_entropy_ = false;
   bool timing_ = false;
   int stripe_h_ = 64;
@@ -453,7 +346,7 @@ class HipHevcPipeline : public EncodePipeline {
   int parity_ = 0;
   Pending prev_;
   int w_ = 0, h_ = 0, ctbw_ = 0, ctbh_ = 0, ypitch_ = 0, cpitch_ = 0;
-  int max_jobs_ = 0, out_stride_ = 0, copy_cap_ = 1 << 30;
+  int out_stride_ = 0;
   size_t levels_bytes_ = 0, meta_bytes_ = 0;
 
   uint8_t* d_frame_[2] = {};
@@ -470,26 +363,13 @@ class HipHevcPipeline : public EncodePipeline {
   int* h_counts_[2] = {};
   int16_t* h_levels_ = nullptr;
   int* h_meta_ = nullptr;
-  uint8_t* h_stage_ = nullptr;
-  size_t h_stage_bytes_ = 0;
-
-  std::vector<void*> device_ptrs_;
-  std::map<uint8_t*, bool> registered_;
 };
 
 }  // namespace
 
 std::unique_ptr<EncodePipeline> make_hip_hevc_pipeline(
     const CaptureSettings& s) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return nullptr;
-  try {
-    return std::make_unique<HipHevcPipeline>(s);
-  } catch (const std::exception& e) {
-    std::fprintf(stderr, "hipflux: HEVC HIP pipeline unavailable: %s\n",
-                 e.what());
-    return nullptr;
-  }
+  return std::make_unique<HipHevcPipeline>(s);
 }
 
 }  // namespace hipflux

@@ -7,15 +7,9 @@
 #include <cstring>
 #include <stdexcept>
 
-namespace hipflux {
+#include "hip_host.h"   // HIP_CHECK
 
-#define HIP_CK(expr)                                                       \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess)                                                  \
-      throw std::runtime_error(std::string("HIP: ") +                      \
-                               hipGetErrorString(_e) + " at " #expr);      \
-  } while (0)
+namespace hipflux {
 
 #define NCCL_CK(expr)                                                      \
   do {                                                                     \
@@ -35,13 +29,13 @@ TileComm::TileComm(int rank, int world, const std::string& uid, int device)
     : rank_(rank), world_(world), device_(device) {
   if (uid.size() != NCCL_UNIQUE_ID_BYTES)
     throw std::runtime_error("bad RCCL unique id size");
-  HIP_CK(hipSetDevice(device));
+  HIP_CHECK(hipSetDevice(device));
   hipStream_t s;
-  HIP_CK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   stream_ = s;
   hipEvent_t e0, e1;
-  HIP_CK(hipEventCreate(&e0));
-  HIP_CK(hipEventCreate(&e1));
+  HIP_CHECK(hipEventCreate(&e0));
+  HIP_CHECK(hipEventCreate(&e1));
   ev0_ = e0;
   ev1_ = e1;
   ncclUniqueId id;
@@ -62,7 +56,7 @@ TileComm::~TileComm() {
 void TileComm::ensure(size_t bytes) {
   if (bytes <= slot_cap_) return;
   if (d_all_) (void)hipFree(d_all_);
-  HIP_CK(hipMalloc(&d_all_, bytes * world_));
+  HIP_CHECK(hipMalloc(&d_all_, bytes * world_));
   slot_cap_ = bytes;
 }
 
@@ -73,7 +67,7 @@ double TileComm::exchange(uintptr_t src_dev, size_t bytes, int schedule) {
   auto c = static_cast<ncclComm_t>(comm_);
   auto* src = reinterpret_cast<void*>(src_dev);
   auto* all = static_cast<uint8_t*>(d_all_);
-  HIP_CK(hipEventRecord(static_cast<hipEvent_t>(ev0_), s));
+  HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(ev0_), s));
   if (schedule == 0) {
     NCCL_CK(ncclAllGather(src, all, bytes, ncclUint8, c, s));
   } else {
@@ -87,11 +81,11 @@ double TileComm::exchange(uintptr_t src_dev, size_t bytes, int schedule) {
                        ncclUint8, p, c, s));
     }
     NCCL_CK(ncclGroupEnd());
-    HIP_CK(hipMemcpyAsync(all + static_cast<size_t>(rank_) * bytes, src,
-                          bytes, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(all + static_cast<size_t>(rank_) * bytes, src,
+                             bytes, hipMemcpyDeviceToDevice, s));
   }
-  HIP_CK(hipEventRecord(static_cast<hipEvent_t>(ev1_), s));
-  HIP_CK(hipEventSynchronize(static_cast<hipEvent_t>(ev1_)));
+  HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(ev1_), s));
+  HIP_CHECK(hipEventSynchronize(static_cast<hipEvent_t>(ev1_)));
   float ms = 0;
   (void)hipEventElapsedTime(&ms, static_cast<hipEvent_t>(ev0_),
                             static_cast<hipEvent_t>(ev1_));
@@ -100,12 +94,12 @@ double TileComm::exchange(uintptr_t src_dev, size_t bytes, int schedule) {
 
 double TileComm::broadcast(uintptr_t buf_dev, size_t bytes, int root) {
   auto s = static_cast<hipStream_t>(stream_);
-  HIP_CK(hipEventRecord(static_cast<hipEvent_t>(ev0_), s));
+  HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(ev0_), s));
   NCCL_CK(ncclBroadcast(reinterpret_cast<void*>(buf_dev),
                         reinterpret_cast<void*>(buf_dev), bytes, ncclUint8,
                         root, static_cast<ncclComm_t>(comm_), s));
-  HIP_CK(hipEventRecord(static_cast<hipEvent_t>(ev1_), s));
-  HIP_CK(hipEventSynchronize(static_cast<hipEvent_t>(ev1_)));
+  HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(ev1_), s));
+  HIP_CHECK(hipEventSynchronize(static_cast<hipEvent_t>(ev1_)));
   float ms = 0;
   (void)hipEventElapsedTime(&ms, static_cast<hipEvent_t>(ev0_),
                             static_cast<hipEvent_t>(ev1_));
@@ -116,10 +110,10 @@ std::vector<uint8_t> TileComm::gathered(int rank, size_t bytes) {
   std::vector<uint8_t> out(bytes);
   if (!d_all_ || bytes > last_bytes_)
     throw std::runtime_error("no gathered payload of that size");
-  HIP_CK(hipMemcpy(out.data(),
-                   static_cast<uint8_t*>(d_all_) +
-                       static_cast<size_t>(rank) * last_bytes_,
-                   bytes, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(out.data(),
+                      static_cast<uint8_t*>(d_all_) +
+                          static_cast<size_t>(rank) * last_bytes_,
+                      bytes, hipMemcpyDeviceToHost));
   return out;
 }
 

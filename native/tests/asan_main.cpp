@@ -3,8 +3,9 @@
 // Python + external Rust); the HIP engine's host code gets real ASan
 // coverage here. Exercises the H.264 stripe encoder (all mode paths,
 // odd sizes, QP extremes), the JPEG encoder, the box downscaler and the
-// NAL assembly helpers with pseudo-random inputs; any heap error or UB
-// aborts with a nonzero exit.
+// NAL assembly helpers with pseudo-random inputs, and the H.264 slice
+// plan over its input range; any heap error or UB aborts with a nonzero
+// exit.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -12,6 +13,7 @@
 
 #include "../cpu/h264/encoder.h"
 #include "../cpu/h264/gpu_entropy.h"
+#include "../cpu/h264/seg_plan.h"
 #include "../cpu/jpeg_enc.h"
 #include "../cpu/opus/celt.h"
 #include "../cpu/scale.h"
@@ -116,6 +118,22 @@ int main() {
       wv = (t % 3 == 0) ? 0 : (t % 3 == 1 ? rnd() : rnd() & 0x03030303);
     std::vector<uint8_t> out;
     h264::assemble_gpu_row_nal(words.data(), nbits, t & 1, t & 2, out);
+  }
+  // H.264 slice plan: every (mbw, mbh, override) must tile the row with
+  // slices of 1..kMaxSegMbw MBs (UBSan covers the divisions)
+  for (int mbw = 1; mbw <= 1024; ++mbw) {
+    for (int mbh : {1, 2, 6, 68, 135, 270, 599}) {
+      for (int ov = -1; ov <= 40; ++ov) {
+        const h264::SegPlan p = h264::seg_plan(mbw, mbh, ov);
+        const int last = mbw - (p.segs - 1) * p.widest;
+        if (p.segs < 1 || p.widest > h264gpu::kMaxSegMbw || last < 1 ||
+            last > p.widest) {
+          std::fprintf(stderr, "bad slice plan at %dx%d override %d\n", mbw,
+                       mbh, ov);
+          return 7;
+        }
+      }
+    }
   }
   std::puts("sanitizer harness ok");
   return 0;

@@ -49,6 +49,7 @@ class VideoRelay:
         self._backlog_bytes = 0
         self._broken_rows: set[int] = set()
         self._task: Optional[asyncio.Task] = None
+        self._stopping = False
         self.dead = False
         # stats
         self.sent_frames = 0
@@ -61,10 +62,14 @@ class VideoRelay:
 
     def start(self) -> None:
         if self._task is None:
+            self._stopping = False
             self._task = asyncio.get_running_loop().create_task(self._run())
 
     async def stop(self) -> None:
         if self._task is not None:
+            # wait_for() in _run swallows a cancel that lands just as its
+            # send completes (CPython < 3.12); the flag ends the loop then
+            self._stopping = True
             self._task.cancel()
             try:
                 await self._task
@@ -95,7 +100,7 @@ class VideoRelay:
 
     # -- consumer task ------------------------------------------------------
     async def _run(self) -> None:
-        while True:
+        while not self._stopping:
             payload, y = await self._backlog.get()
             self._backlog_bytes -= len(payload)
             t0 = time.monotonic()

@@ -44,8 +44,9 @@ def _register(s: Suite):
 _register(Suite(
     "codecs", "Entropy/transform conformance vs the from-spec decoders "
     "(H.264, HEVC, JPEG, Opus)", 0,
-    ("test_h264.py", "test_h264_content.py", "test_hevc.py", "test_jpeg.py",
-     "test_opus.py", "test_opus_js.py", "test_rate_control.py")))
+    ("test_h264.py", "test_h264_content.py", "test_h264_seg_plan.py",
+     "test_hevc.py", "test_jpeg.py", "test_opus.py", "test_opus_js.py",
+     "test_rate_control.py")))
 _register(Suite(
     "engine", "Capture engine, damage, scaling, audio engine, recording",
     0, ("test_engine.py", "test_engine_h264.py", "test_audio.py",
@@ -75,7 +76,8 @@ _register(Suite(
 _register(Suite(
     "gpu", "Byte-identity + numerics on a real MI355X", 2,
     ("test_gpu_h264.py", "test_gpu_h264_recon.py", "test_gpu_hevc.py",
-     "test_gpu_jpeg.py", "test_gpu_tile_comm.py"), marker="gpu"))
+     "test_gpu_jpeg.py", "test_gpu_pipeline_host.py",
+     "test_gpu_tile_comm.py"), marker="gpu"))
 _register(Suite(
     "perf", "Bench contract guards (driver JSON line shape)", 3,
     ("test_bench_contract.py",)))

@@ -88,3 +88,28 @@ def test_fifo_delivery(loop):
         await r.stop()
 
     loop.run_until_complete(main())
+
+
+def test_stop_returns_when_cancel_lands_as_a_send_completes(loop):
+    """asyncio.wait_for() returns its result and swallows a cancel that
+    arrives once the awaited send has finished but before its waiter woke
+    (CPython < 3.12). stop() must still end the relay task: the WebSocket
+    handler awaits it before it promotes the next controller."""
+    async def main():
+        gate = asyncio.get_running_loop().create_future()
+
+        async def send(b):
+            await gate
+
+        r = VideoRelay(send, lambda: None)
+        r.start()
+        r.offer(b"k", y=0, is_keyframe=True)
+        await asyncio.sleep(0.05)          # the relay is inside the send
+        gate.set_result(None)              # the send completes ...
+        stopper = asyncio.ensure_future(r.stop())   # ... as the cancel lands
+        done, _ = await asyncio.wait({stopper}, timeout=2)
+        if not done:
+            stopper.cancel()
+        assert done, "stop() hung: the relay task outlived its cancel"
+
+    loop.run_until_complete(main())
