@@ -7,17 +7,24 @@ namespace hipflux {
 
 void upload_dct_tables(hipStream_t stream);
 
+// chroma_w/chroma_h (4:2:0 only): size of the chroma grid to produce, when
+// larger than ceil(width/2) x ceil(height/2); samples past the picture come
+// from pixel reads clamped to its last column and row. 0 = unpadded.
 void launch_bgrx_to_planes(const void* bgrx, int width, int height,
                            int stride_px, uint8_t* yp, uint8_t* cbp,
                            uint8_t* crp, int ypitch, int cpitch,
-                           bool fullcolor, hipStream_t stream);
+                           bool fullcolor, hipStream_t stream,
+                           int chroma_w = 0, int chroma_h = 0);
 
 // DCT+quant one plane into MCU-scan-order int16 blocks (see .hip for the
-// output indexing contract shared with the CPU entropy coder).
+// output indexing contract shared with the CPU entropy coder). Covers the
+// whole mcux x mcuy MCU grid (2x2 luma blocks per MCU in 4:2:0), reading
+// past pw x ph by edge replication.
 void launch_dct_quant(const uint8_t* plane, int pw, int ph, int pitch,
                       const float* rq, int16_t* out, int plane_kind,
-                      bool fullcolor, int mcux, int mcu_rows_per_stripe,
-                      int stripe_mcu_count, hipStream_t stream);
+                      bool fullcolor, int mcux, int mcuy,
+                      int mcu_rows_per_stripe, int stripe_mcu_count,
+                      hipStream_t stream);
 
 }  // namespace hipflux
 

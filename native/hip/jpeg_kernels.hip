@@ -37,14 +37,17 @@ __device__ inline float dev_cr(float r, float g, float b) {
 
 // ---------------------------------------------------------------------------
 // BGRX -> planar Y + 2x2-subsampled Cb/Cr. Grid-stride over 2x2 quads.
-// Edge replication for odd sizes is handled by clamping reads.
+// Edge replication for odd sizes is handled by clamping reads. The quad
+// grid is cw x ch: ceil(width/2) x ceil(height/2) for the video paths; the
+// JPEG path asks for the MCU-padded chroma size, so that its pad samples
+// come from clamped PIXEL reads like cpu/jpeg_enc.cpp's (replicating the
+// last chroma sample instead would average the last two columns/rows).
 __global__ void k_bgrx_to_planes_420(const uchar4* __restrict__ bgrx,
                                      int width, int height, int stride_px,
                                      uint8_t* __restrict__ yp,
                                      uint8_t* __restrict__ cbp,
                                      uint8_t* __restrict__ crp,
-                                     int ypitch, int cpitch) {
-  int cw = (width + 1) >> 1, ch = (height + 1) >> 1;
+                                     int ypitch, int cpitch, int cw, int ch) {
   int total = cw * ch;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += gridDim.x * blockDim.x) {
@@ -108,10 +111,15 @@ __global__ void __launch_bounds__(256)
     k_dct_quant(const uint8_t* __restrict__ plane, int pw, int ph, int pitch,
                 const float* __restrict__ rq,  // reciprocal quant, natural
                 int16_t* __restrict__ out, int plane_kind, bool fullcolor,
-                int mcux, int mcu_rows_per_stripe, int stripe_mcu_count) {
+                int mcux, int mcuy, int mcu_rows_per_stripe,
+                int stripe_mcu_count) {
   int wave = threadIdx.x >> 6;          // 4 waves per workgroup
   int lane = threadIdx.x & 63;
-  int bx_count = (pw + 7) >> 3, by_count = (ph + 7) >> 3;
+  // the MCU-padded block grid, not ceil(pw/8) x ceil(ph/8): every slot the
+  // entropy coder reads gets written; blocks past the plane replicate its
+  // edge through the clamped reads below
+  int per_mcu_side = (!fullcolor && plane_kind == 0) ? 2 : 1;
+  int bx_count = per_mcu_side * mcux, by_count = per_mcu_side * mcuy;
   int nblocks = bx_count * by_count;
   int block = blockIdx.x * 4 + wave;
   if (block >= nblocks) return;
@@ -183,14 +191,17 @@ void upload_dct_tables(hipStream_t stream) {
 void launch_bgrx_to_planes(const void* bgrx, int width, int height,
                            int stride_px, uint8_t* yp, uint8_t* cbp,
                            uint8_t* crp, int ypitch, int cpitch,
-                           bool fullcolor, hipStream_t stream) {
+                           bool fullcolor, hipStream_t stream,
+                           int chroma_w, int chroma_h) {
   int threads = 256;
   if (!fullcolor) {
-    int total = ((width + 1) / 2) * ((height + 1) / 2);
+    int cw = chroma_w ? chroma_w : (width + 1) / 2;
+    int ch = chroma_h ? chroma_h : (height + 1) / 2;
+    int total = cw * ch;
     int blocks = min((total + threads - 1) / threads, 2048);
     hipLaunchKernelGGL(k_bgrx_to_planes_420, dim3(blocks), dim3(threads), 0,
                        stream, (const uchar4*)bgrx, width, height, stride_px,
-                       yp, cbp, crp, ypitch, cpitch);
+                       yp, cbp, crp, ypitch, cpitch, cw, ch);
   } else {
     int total = width * height;
     int blocks = min((total + threads - 1) / threads, 2048);
@@ -202,13 +213,14 @@ void launch_bgrx_to_planes(const void* bgrx, int width, int height,
 
 void launch_dct_quant(const uint8_t* plane, int pw, int ph, int pitch,
                       const float* rq, int16_t* out, int plane_kind,
-                      bool fullcolor, int mcux, int mcu_rows_per_stripe,
-                      int stripe_mcu_count, hipStream_t stream) {
-  int bx = (pw + 7) / 8, by = (ph + 7) / 8;
-  int nblocks = bx * by;
+                      bool fullcolor, int mcux, int mcuy,
+                      int mcu_rows_per_stripe, int stripe_mcu_count,
+                      hipStream_t stream) {
+  int per_mcu_side = (!fullcolor && plane_kind == 0) ? 2 : 1;
+  int nblocks = per_mcu_side * mcux * per_mcu_side * mcuy;
   int wgs = (nblocks + 3) / 4;
   hipLaunchKernelGGL(k_dct_quant, dim3(wgs), dim3(256), 0, stream, plane, pw,
-                     ph, pitch, rq, out, plane_kind, fullcolor, mcux,
+                     ph, pitch, rq, out, plane_kind, fullcolor, mcux, mcuy,
                      mcu_rows_per_stripe, stripe_mcu_count);
 }
 

@@ -66,13 +66,17 @@ class HipJpegPipeline : public EncodePipeline {
                              prod_stream_));
 
     const int stride_px = frame.stride / 4;
-    launch_bgrx_to_planes(d_frame2_[par], w_, h_, stride_px, d_y_, d_cb_,
-                          d_cr_, ypitch_, cpitch_, fullcolor, prod_stream_);
-
     const int stripe_h = std::max(16, settings_.stripe_height & ~15);
     const int mcu = fullcolor ? 8 : 16;
     const int mcux = (w_ + mcu - 1) / mcu;
     const int mcuy = (h_ + mcu - 1) / mcu;
+    // 4:2:0 chroma is produced at its MCU-padded size: the pad samples are
+    // quads of clamped pixel reads, as in jpeg_encode_bgrx
+    const int cwp = mcux * 8, chp = mcuy * 8;
+    launch_bgrx_to_planes(d_frame2_[par], w_, h_, stride_px, d_y_, d_cb_,
+                          d_cr_, ypitch_, cpitch_, fullcolor, prod_stream_,
+                          cwp, chp);
+
     const int rows_per_stripe = stripe_h / mcu;
     const int stripe_mcu_count = rows_per_stripe * mcux;
     const int per_mcu_real = fullcolor ? 3 : 6;
@@ -80,23 +84,23 @@ class HipJpegPipeline : public EncodePipeline {
     int16_t* d_coeff = d_coeff2_[par];
     if (!fullcolor) {
       launch_dct_quant(d_y_, w_, h_, ypitch_, d_rqy_, d_coeff, 0, false,
-                       mcux, rows_per_stripe, stripe_mcu_count,
+                       mcux, mcuy, rows_per_stripe, stripe_mcu_count,
                        prod_stream_);
-      launch_dct_quant(d_cb_, cw_, ch_, cpitch_, d_rqc_, d_coeff, 1, false,
-                       mcux, rows_per_stripe, stripe_mcu_count,
+      launch_dct_quant(d_cb_, cwp, chp, cpitch_, d_rqc_, d_coeff, 1, false,
+                       mcux, mcuy, rows_per_stripe, stripe_mcu_count,
                        prod_stream_);
-      launch_dct_quant(d_cr_, cw_, ch_, cpitch_, d_rqc_, d_coeff, 2, false,
-                       mcux, rows_per_stripe, stripe_mcu_count,
+      launch_dct_quant(d_cr_, cwp, chp, cpitch_, d_rqc_, d_coeff, 2, false,
+                       mcux, mcuy, rows_per_stripe, stripe_mcu_count,
                        prod_stream_);
     } else {
       launch_dct_quant(d_y_, w_, h_, ypitch_, d_rqy_, d_coeff, 0, true,
-                       mcux, rows_per_stripe, stripe_mcu_count,
+                       mcux, mcuy, rows_per_stripe, stripe_mcu_count,
                        prod_stream_);
       launch_dct_quant(d_cb_, w_, h_, ypitch_, d_rqc_, d_coeff, 1, true,
-                       mcux, rows_per_stripe, stripe_mcu_count,
+                       mcux, mcuy, rows_per_stripe, stripe_mcu_count,
                        prod_stream_);
       launch_dct_quant(d_cr_, w_, h_, ypitch_, d_rqc_, d_coeff, 2, true,
-                       mcux, rows_per_stripe, stripe_mcu_count,
+                       mcux, mcuy, rows_per_stripe, stripe_mcu_count,
                        prod_stream_);
     }
     HIP_CHECK(hipEventRecord(jev_dct_[par], prod_stream_));
@@ -267,16 +271,16 @@ class HipJpegPipeline : public EncodePipeline {
     prod_stream_.sync();
     arena_.release();
     w_ = h_ = 0;   // until everything below succeeded: a throw retries
-    cw_ = (w + 1) / 2;
-    ch_ = (h + 1) / 2;
     ypitch_ = (w + 255) & ~255;
-    cpitch_ = (cw_ + 255) & ~255;
+    cpitch_ = ((w + 1) / 2 + 255) & ~255;
     for (int i = 0; i < 2; ++i)
       arena_.dev(d_frame2_[i], static_cast<size_t>(w) * h * 4);
     arena_.dev(d_y_, static_cast<size_t>(ypitch_) * h);
-    // chroma buffers sized for 4:4:4 (the larger case)
-    arena_.dev(d_cb_, static_cast<size_t>(ypitch_) * h);
-    arena_.dev(d_cr_, static_cast<size_t>(ypitch_) * h);
+    // chroma buffers sized for 4:4:4 (the larger case), and for the
+    // MCU-padded 4:2:0 chroma rows, which exceed h when h < 16
+    const size_t crows = std::max(h, (h + 15) / 16 * 8);
+    arena_.dev(d_cb_, static_cast<size_t>(ypitch_) * crows);
+    arena_.dev(d_cr_, static_cast<size_t>(ypitch_) * crows);
     // coefficients: 6 blocks/MCU covers both 420 (6) and 444 (3)
     size_t mcux = (w + 7) / 8, mcuy = (h + 7) / 8;  // worst case 444
     size_t coeff_count = mcux * mcuy * 6 * 64;
@@ -353,7 +357,7 @@ class HipJpegPipeline : public EncodePipeline {
   int16_t* h_coeff_ = nullptr;
   float* d_rqy_ = nullptr;
   float* d_rqc_ = nullptr;
-  int w_ = 0, h_ = 0, cw_ = 0, ch_ = 0, ypitch_ = 0, cpitch_ = 0;
+  int w_ = 0, h_ = 0, ypitch_ = 0, cpitch_ = 0;
   int cur_quality_ = -1;
 };
 

@@ -4,10 +4,14 @@ Runs only on a box with an MI355X. Verifies:
   * the HIP pipeline actually engages (no silent CPU fallback)
   * GPU-encoded stripes decode with PIL and match the source (PSNR)
   * GPU output is coefficient-compatible with the CPU reference encoder
+  * every coefficient of every emitted stripe, pad blocks included, is a
+    rounding of a float64 DCT of the stripe's pixels (jpeg_ref.py), at odd
+    sizes, four qualities, under a damage mask and across read-back growth
 """
 
 import io
 import math
+import re
 import threading
 import time
 
@@ -167,3 +171,158 @@ def test_gpu_jpeg_entropy_matches_cpu_packer():
     img = Image.open(io.BytesIO(bytes(sorted(g444[0],
                                              key=lambda t: t[1])[0][0])))
     assert img.size == (w, 64)
+
+
+# ---- every coefficient against a float64 DCT ----------------------------------
+#
+# The tests above compare the GPU with itself or by PSNR. These decode every
+# emitted stripe with the from-spec decoder of jpeg_ref.py and hold 100 % of
+# its coefficients, pad blocks included, to the float64 reference of the
+# stripe's own pixels (established on the CPU encoder and on PIL in
+# test_jpeg.py).
+
+import jpeg_ref
+from hipflux import _native
+
+# (fullcolor, w, h, stripe_h): sizes at which the kernels take another path
+COEFF_CASES = [
+    (False, 16, 16, 16),     # one MCU: 6 items in a 256-thread scan
+    (False, 17, 17, 16),     # both pads 1 pixel wide, second stripe 1 row high
+    (False, 328, 72, 32),    # w%16 = h%16 = 8: luma pad blocks past ceil(w/8)
+    (False, 322, 150, 64),   # the size the HEVC test uses
+    (False, 333, 47, 32),    # pad > 8; chroma clamp on an odd width
+    (False, 712, 24, 16),    # 45 MCUs x 6 = 270 items > 256 threads
+    (True, 9, 9, 16),        # 3-item rows at the top, 6 items at most
+    (True, 324, 36, 16),     # odd block counts; stripes cover two MCU rows
+    (True, 700, 24, 16),     # 88 x 3 = 264 items > 256 threads
+]
+# all of them at quality 80; the two with every pad also at the extremes
+COEFF_RUNS = [c + (80,) for c in COEFF_CASES] + [
+    c + (q,) for c in (COEFF_CASES[2], COEFF_CASES[7]) for q in (1, 35, 100)]
+
+
+def check_stripes(emitted, frame, w, h, stripe_h, quality, fullcolor,
+                  expect_y=None):
+    """Hold every stripe emitted for one frame to the reference; returns
+    (coefficients checked, worst |c-r|-0.5, allowance there, coefficients
+    that differ from the CPU encoder's)."""
+    mcu = 8 if fullcolor else 16
+    if expect_y is None:
+        expect_y = list(range(0, h, stripe_h))
+    assert sorted(y for _, y, _, _ in emitted) == expect_y
+    checked = cpu_diff = 0
+    worst = (-1.0, 0.0)
+    for data, y0, sh, _ in emitted:
+        assert sh == min(stripe_h, h - y0)
+        d = jpeg_ref.decode_coeffs(bytes(data))
+        assert (d["width"], d["height"], d["fullcolor"]) == (w, sh, fullcolor)
+        assert d["dri"] == -(-w // mcu)
+        px = frame[y0:y0 + sh]
+        cpu = jpeg_ref.decode_coeffs(_native._jpeg_encode_restart(
+            px.tobytes(), w, sh, quality, fullcolor))
+        assert np.array_equal(cpu["qy"], d["qy"])
+        assert np.array_equal(cpu["qc"], d["qc"])
+        n = int((cpu["blocks"] != d["blocks"]).sum())
+        cpu_diff += n
+        ref = jpeg_ref.reference_coeff_real(px, w, sh, d["qy"], d["qc"],
+                                            fullcolor)
+        try:
+            st = jpeg_ref.check_coeffs(d, ref, stripe=y0)
+        except AssertionError as e:
+            raise AssertionError(
+                f"{e} [{n} coefficients of this stripe differ from the CPU "
+                f"encoder's]") from None
+        checked += st["checked"]
+        worst = max(worst, (st["worst_excess"], st["worst_allow"]))
+    return checked, worst[0], worst[1], cpu_diff
+
+
+def report(tag, results):
+    checked = sum(r[0] for r in results)
+    excess, allow = max((r[1], r[2]) for r in results)
+    print(f"\n{tag}: {checked} coefficients, worst |c-r|-0.5 = {excess:.3e} "
+          f"(allowance there {allow:.3e}), {sum(r[3] for r in results)} "
+          f"differ from the CPU encoder")
+
+
+@pytest.mark.parametrize(
+    "fullcolor,w,h,stripe_h,quality", COEFF_RUNS,
+    ids=[f"{'444' if f else '420'}-{w}x{h}-q{q}"
+         for f, w, h, _, q in COEFF_RUNS])
+def test_gpu_coefficients_round_the_float64_reference(fullcolor, w, h,
+                                                      stripe_h, quality):
+    """Noise and structures through the HIP pipeline: every stripe decodes
+    strictly, carries the right size and restart interval, and every one
+    of its coefficients is a rounding of the float64 reference."""
+    require_gpu()
+    frames = [jpeg_ref.content_noise(w, h, 4000 + w),
+              jpeg_ref.content_structures(w, h)]
+    out = _native._pipeline_encode("gpu", frames, w, h, quality, stripe_h, 0,
+                                   False, fullcolor)
+    assert len(out) == len(frames)
+    results = [check_stripes(out[i], frames[i], w, h, stripe_h, quality,
+                             fullcolor) for i in range(len(frames))]
+    report(f"{'444' if fullcolor else '420'} {w}x{h} q{quality}", results)
+
+
+def test_gpu_damage_mask_emits_exactly_the_masked_stripes():
+    """encode_mask with JPEG: only the masked-in stripes come out, each is
+    right by itself and byte-equal to the same stripe of an unmasked run."""
+    require_gpu()
+    w, h, stripe_h, quality = 328, 136, 32, 80
+    T, F = True, False
+    masks = [[T, T, T, T, T], [F, T, F, T, T], [F, F, F, F, T]]
+    frames = [jpeg_ref.content_noise(w, h, 4500 + i) for i in range(3)]
+    full = _native._pipeline_encode("gpu", frames, w, h, quality, stripe_h,
+                                    0, False, False)
+    part = _native._pipeline_encode("gpu", frames, w, h, quality, stripe_h,
+                                    0, False, False, encode_mask=masks)
+    results = []
+    for fi, mask in enumerate(masks):
+        want_y = [i * stripe_h for i, m in enumerate(mask) if m]
+        results.append(check_stripes(part[fi], frames[fi], w, h, stripe_h,
+                                     quality, False, expect_y=want_y))
+        whole = {y: bytes(d) for d, y, _, _ in full[fi]}
+        assert sorted(whole) == list(range(0, h, stripe_h))
+        for d, y, _, _ in part[fi]:
+            assert bytes(d) == whole[y], \
+                f"frame {fi} stripe {y}: differs from the unmasked run"
+    report("masked 420 328x136 q80", results)
+
+
+def test_gpu_readback_growth_refetches_whole_rows():
+    """Flat, flat, noise, flat, noise at quality 95 with one frame in
+    flight: a noise frame's rows outgrow the compacted read-back sized by
+    the flat frame before it (2 * max + 64 words), so the rows are
+    fetched again in full. Every frame is right by itself and byte-equal
+    to the synchronous run."""
+    require_gpu()
+    w, h, stripe_h, quality = 328, 72, 32, 95
+    flat = np.full((h, w, 4), 255, np.uint8)
+    flat[:, :, :3] = 91
+    frames = [flat, flat.copy(), jpeg_ref.content_noise(w, h, 4600),
+              flat.copy(), jpeg_ref.content_noise(w, h, 4601)]
+    runs = [_native._pipeline_encode("gpu", frames, w, h, quality, stripe_h,
+                                     0, False, False, pipeline_depth=depth)
+            for depth in (2, 1)]
+    # the premise, in 32-bit words per MCU row (stuffing aside): every
+    # noise row is longer than the cap a flat frame leaves behind
+    def row_words(frame_out):
+        rows = []
+        for d, _, _, _ in frame_out:
+            d = bytes(d)
+            scan = d[d.index(b"\xff\xda") + 14:-2]
+            rows += [(len(r) + 3) // 4 + 1
+                     for r in re.split(rb"\xff[\xd0-\xd7]", scan)]
+        assert len(rows) == 5
+        return rows
+    words = [row_words(fr) for fr in runs[0]]
+    for noise, before in ((2, 0), (2, 1), (4, 3)):
+        assert min(words[noise]) > 2 * max(words[before]) + 64
+    results = [check_stripes(runs[0][i], frames[i], w, h, stripe_h, quality,
+                             False) for i in range(len(frames))]
+    for i in range(len(frames)):
+        assert sorted((y, bytes(d)) for d, y, _, _ in runs[0][i]) == \
+            sorted((y, bytes(d)) for d, y, _, _ in runs[1][i]), \
+            f"frame {i}: depth 2 differs from depth 1"
+    report("growth 420 328x72 q95", results)
