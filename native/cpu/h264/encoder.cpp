@@ -8,6 +8,7 @@
 #include "bitwriter.h"
 #include "cavlc.h"
 #include "deblock.h"
+#include "headers.h"
 #include "transform.h"
 
 namespace hipflux {
@@ -1083,65 +1084,6 @@ struct StripeEncoder::Impl {
     ctx.skip_run = 0;
   }
 };
-
-namespace {
-
-// SPS for High 4:4:4 Predictive with separate colour planes: each plane
-// decodes as a monochrome picture (ChromaArrayType == 0), so CropUnitX/Y
-// are 1 (no /2 on the crop amounts, unlike 4:2:0).
-void write_sps_444(std::vector<uint8_t>& out, int mbw, int mbh, int w,
-                   int h, int level_idc) {
-  BitWriter b;
-  b.u(244, 8);  // profile_idc: High 4:4:4 Predictive
-  b.u(0, 8);    // no constraint flags
-  b.u(level_idc, 8);
-  b.ue(0);      // sps id
-  b.ue(3);      // chroma_format_idc: 4:4:4
-  b.u(1, 1);    // separate_colour_plane_flag
-  b.ue(0);      // bit_depth_luma_minus8
-  b.ue(0);      // bit_depth_chroma_minus8
-  b.u(0, 1);    // qpprime_y_zero_transform_bypass
-  b.u(0, 1);    // seq_scaling_matrix_present
-  b.ue(12);     // log2_max_frame_num_minus4 -> 16-bit frame_num
-  b.ue(2);      // pic_order_cnt_type = 2
-  b.ue(1);      // max_num_ref_frames
-  b.u(0, 1);    // gaps_in_frame_num_value_allowed
-  b.ue(mbw - 1);
-  b.ue(mbh - 1);
-  b.u(1, 1);    // frame_mbs_only
-  b.u(1, 1);    // direct_8x8_inference
-  int crop_r = mbw * 16 - w, crop_b = mbh * 16 - h;
-  if (crop_r || crop_b) {
-    b.u(1, 1);
-    b.ue(0);
-    b.ue(crop_r);
-    b.ue(0);
-    b.ue(crop_b);
-  } else {
-    b.u(0, 1);
-  }
-  // VUI: BT.601 full range, as in the 4:2:0 SPS
-  b.u(1, 1);
-  b.u(0, 1);
-  b.u(0, 1);
-  b.u(1, 1);
-  b.u(5, 3);
-  b.u(1, 1);
-  b.u(1, 1);
-  b.u(6, 8);
-  b.u(6, 8);
-  b.u(6, 8);
-  b.u(0, 1);
-  b.u(0, 1);
-  b.u(0, 1);
-  b.u(0, 1);
-  b.u(0, 1);
-  b.u(0, 1);
-  b.rbsp_trailing();
-  b.emit_nal(out, 3, 7);
-}
-
-}  // namespace
 
 StripeEncoder::StripeEncoder(int width, int height, bool deblock,
                              bool fullcolor)

@@ -36,8 +36,11 @@ struct RowCtx {
 
 // Encode one intra MB from the GPU level buffer. Mirrors
 // encoder.cpp::encode_i16's entropy section exactly.
+// mono (a Hi444 separate colour plane, ChromaArrayType == 0): the chroma
+// region of the levels block is never written and must not be read; no
+// intra_chroma_pred_mode, cbp_chroma 0.
 void entropy_i16(BitWriter& bw, const int16_t* L, int m0, int m1, int qp,
-                 bool p_slice, RowCtx& ctx) {
+                 bool p_slice, bool mono, RowCtx& ctx) {
   const int luma_mode = (m0 >> 2) & 7;
   // chroma pipeline reports its mode via meta word 1 (unused for intra)
   const int chroma_mode = m1 & 7;
@@ -54,26 +57,29 @@ void entropy_i16(BitWriter& bw, const int16_t* L, int m0, int m1, int qp,
     }
   }
   const int cbp_luma = any_ac ? 15 : 0;
+  // read only when cbp_chroma > 0, which mono never reaches
   int cdc[2][4];
   bool any_cdc = false;
-  for (int comp = 0; comp < 2; ++comp)
-    for (int i = 0; i < 4; ++i) {
-      cdc[comp][i] = L[kChromaDcOff + comp * 4 + i];
-      any_cdc |= cdc[comp][i] != 0;
-    }
   int czz[8][15];
   bool any_cac = false;
-  for (int b = 0; b < 8; ++b)
-    for (int i = 1; i < 16; ++i) {
-      czz[b][i - 1] = L[kChromaAcOff + b * 16 + kZigzag4[i]];
-      any_cac |= czz[b][i - 1] != 0;
-    }
+  if (!mono) {
+    for (int comp = 0; comp < 2; ++comp)
+      for (int i = 0; i < 4; ++i) {
+        cdc[comp][i] = L[kChromaDcOff + comp * 4 + i];
+        any_cdc |= cdc[comp][i] != 0;
+      }
+    for (int b = 0; b < 8; ++b)
+      for (int i = 1; i < 16; ++i) {
+        czz[b][i - 1] = L[kChromaAcOff + b * 16 + kZigzag4[i]];
+        any_cac |= czz[b][i - 1] != 0;
+      }
+  }
   const int cbp_chroma = any_cac ? 2 : (any_cdc ? 1 : 0);
 
   const int i16_type =
       1 + luma_mode + 4 * cbp_chroma + 12 * (cbp_luma ? 1 : 0);
   bw.ue(p_slice ? 5 + i16_type : i16_type);
-  bw.ue(chroma_mode);
+  if (!mono) bw.ue(chroma_mode);
   bw.se(0);  // mb_qp_delta
 
   uint8_t new_luma[16] = {};
@@ -215,6 +221,24 @@ void entropy_p16(BitWriter& bw, const int16_t* L, int mvx, int mvy,
   }
 }
 
+// Monochrome P_L0_16x16: the row kernel re-codes every inter MB with a
+// non-zero residual as I16x16, so the MB is its motion vector alone --
+// coded_block_pattern codeNum 0, no mb_qp_delta, and the levels block is
+// not consulted.
+void entropy_p16_mono(BitWriter& bw, int mvx, int mvy, RowCtx& ctx) {
+  bw.ue(0);  // P_L0_16x16
+  int mvpx = (ctx.have_left && ctx.left_is_inter) ? ctx.left_mvx : 0;
+  int mvpy = (ctx.have_left && ctx.left_is_inter) ? ctx.left_mvy : 0;
+  bw.se(mvx - mvpx);
+  bw.se(mvy - mvpy);
+  bw.ue(0);  // coded_block_pattern 0
+  ctx.have_left = true;
+  ctx.left_is_inter = true;
+  ctx.left_mvx = mvx;
+  ctx.left_mvy = mvy;
+  std::fill(ctx.left_luma_nc, ctx.left_luma_nc + 4, 0);
+}
+
 }  // namespace
 
 void encode_stripe_from_gpu(const GpuStripeParams& p,
@@ -240,9 +264,11 @@ void encode_seg_nal_from_gpu(const GpuStripeParams& p, int row, int mbx0,
   {
     BitWriter b;
     write_slice_header_bits(b, p.idr, row * mbw_stripe + mbx0, p.frame_num,
-                            p.idr_pic_id, p.qp, p.deblock ? 2 : 1);
+                            p.idr_pic_id, p.qp, p.deblock ? 2 : 1,
+                            p.colour_plane);
+    const bool mono = p.colour_plane >= 0;
     RowCtx ctx;
-    const size_t mb_base = (size_t)(p.mb_row0 + row) * p.mbw;
+    const size_t mb_base = p.mb_base + (size_t)(p.mb_row0 + row) * p.mbw;
     for (int mbx = mbx0; mbx < mbx0 + seg_mbw; ++mbx) {
       const int16_t* L = p.levels + (mb_base + mbx) * kLevelsPerMb;
       const int* M = p.meta + (mb_base + mbx) * kMetaPerMb;
@@ -267,10 +293,13 @@ void encode_seg_nal_from_gpu(const GpuStripeParams& p, int row, int mbx0,
       if (!p.idr && mode == h264gpu::kInter) {
         int mvx = (int16_t)(m1 & 0xFFFF);
         int mvy = m1 >> 16;
-        entropy_p16(b, L, mvx, mvy, ctx);
+        if (mono)
+          entropy_p16_mono(b, mvx, mvy, ctx);
+        else
+          entropy_p16(b, L, mvx, mvy, ctx);
         continue;
       }
-      entropy_i16(b, L, m0, m1, p.qp, !p.idr, ctx);
+      entropy_i16(b, L, m0, m1, p.qp, !p.idr, mono, ctx);
     }
     if (!p.idr && ctx.skip_run > 0) b.ue(ctx.skip_run);
     b.rbsp_trailing();

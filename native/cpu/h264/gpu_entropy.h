@@ -3,6 +3,7 @@
 // frame: SPS/PPS (on IDR) + one slice NAL per MB row.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -22,6 +23,12 @@ struct GpuStripeParams {
   bool deblock = false;   // slice headers signal idc=2
   uint32_t frame_num;
   uint32_t idr_pic_id;
+  // Hi444 separate colour planes: the plane this stripe picture codes
+  // (-1 = 4:2:0), written as colour_plane_id and selecting the monochrome
+  // macroblock syntax; mb_base is the MB index at which the plane's
+  // region of levels/meta starts.
+  int colour_plane = -1;
+  size_t mb_base = 0;
 };
 
 void encode_stripe_from_gpu(const GpuStripeParams& p,

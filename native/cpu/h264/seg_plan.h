@@ -37,15 +37,20 @@ struct SegPlan {
 // from the widest slice, so no request can leave a zero-width trailing
 // slice: 5 slices over 16 MBs plan as 4 of 4, and a request above mbw
 // degrades to one MB per slice.
-inline SegPlan seg_plan(int mbw, int mbh, int override_segs = 0) {
+// planes > 1 (Hi444 separate colour planes: every MB row is coded once
+// per plane, all in the same launches) shapes for mbh * planes concurrent
+// rows; planes == 1 is the 4:2:0 plan.
+inline SegPlan seg_plan(int mbw, int mbh, int override_segs = 0,
+                        int planes = 1) {
   const int min_segs = (mbw + h264gpu::kMaxSegMbw - 1) / h264gpu::kMaxSegMbw;
   int segs;
   if (override_segs >= 1) {
     segs = std::max(min_segs, override_segs);
   } else {
-    const int fill = (256 + mbh - 1) / std::max(1, mbh);
+    const int rows = std::max(1, mbh * planes);
+    const int fill = (256 + rows - 1) / rows;
     const int chain_cap = std::max(1, mbw / 30);
-    const int job_cap = std::max(1, 256 / std::max(1, mbh));
+    const int job_cap = std::max(1, 256 / rows);
     const int shaped = job_cap > 1 ? std::min(std::min(fill, job_cap),
                                               std::min(chain_cap, 8))
                                    : std::min(chain_cap, 8);

@@ -251,6 +251,11 @@ struct MbInfo {
 #define MB_CBPL(f) (((f) >> 8) & 1)
 #define MB_CBPC(f) (((f) >> 9) & 3)
 
+// MONO (a Hi444 separate colour plane): the chroma region of the levels
+// block and the chroma mode in meta word 1 are never written, so neither
+// is read; an inter MB carries no residual at all (the row kernel
+// re-codes those as I16x16), so its luma totals are zero by construction.
+template <bool MONO>
 __device__ void precompute_mb(const int16_t* levels, const int* meta,
                               size_t mb_index, bool i_slice, MbInfo* out) {
   int m0 = meta[mb_index * kMetaPerMb + 0];
@@ -259,7 +264,7 @@ __device__ void precompute_mb(const int16_t* levels, const int* meta,
   out->mvx = (short)(m1 & 0xFFFF);
   out->mvy = (short)(m1 >> 16);
   int cbp_luma1 = 0, cbp_chroma = 0;
-  if (mode == kIntra || mode == kInter) {
+  if (mode == kIntra || (!MONO && mode == kInter)) {
     // intra: luma totals over the 15 AC coeffs; inter: full 16-coeff
     // blocks (no DC Hadamard for inter residuals)
     const int first = (mode == kIntra) ? 1 : 0;
@@ -271,12 +276,16 @@ __device__ void precompute_mb(const int16_t* levels, const int* meta,
       any_ac |= t;
     }
     int any_cac = 0, any_cdc = 0;
-    for (int b = 0; b < 8; ++b) {
-      int t = blk_total16v(L, kChromaAcOff + b * 16, 1);
-      out->ctot[b] = (uint8_t)t;
-      any_cac |= t;
+    if constexpr (!MONO) {
+      for (int b = 0; b < 8; ++b) {
+        int t = blk_total16v(L, kChromaAcOff + b * 16, 1);
+        out->ctot[b] = (uint8_t)t;
+        any_cac |= t;
+      }
+      for (int i = 0; i < 8; ++i) any_cdc |= L[kChromaDcOff + i] != 0;
+    } else {
+      for (int b = 0; b < 8; ++b) out->ctot[b] = 0;
     }
-    for (int i = 0; i < 8; ++i) any_cdc |= L[kChromaDcOff + i] != 0;
     cbp_luma1 = any_ac ? 1 : 0;
     cbp_chroma = any_cac ? 2 : (any_cdc ? 1 : 0);
   } else {
@@ -284,7 +293,7 @@ __device__ void precompute_mb(const int16_t* levels, const int* meta,
     for (int b = 0; b < 8; ++b) out->ctot[b] = 0;
   }
   // chroma mode rides in meta word 1 for intra MBs (see k_h264_rows)
-  int cmode = (mode == kIntra) ? (m1 & 7) : 0;
+  int cmode = (!MONO && mode == kIntra) ? (m1 & 7) : 0;
   out->flags = (short)(mode | (((m0 >> 2) & 7) << 2) | (cmode << 5) |
                        (cbp_luma1 << 8) | (cbp_chroma << 9));
 }
@@ -314,7 +323,12 @@ __device__ inline int lds_chroma_nc(const MbInfo* info, int mbx, int comp,
 }
 
 // ---- the kernel -------------------------------------------------------------
-__global__ void __launch_bounds__(1024) k_h264_cavlc_rows(
+// One body, two kernels: MONO = false is the 4:2:0 stream; MONO = true
+// packs a Hi444 separate-colour-plane slice -- colour_plane_id in the
+// slice header, no intra_chroma_pred_mode, P_L0_16x16 as mv +
+// coded_block_pattern codeNum 0, chroma slots 18..27 empty.
+template <bool MONO>
+__device__ __forceinline__ void cavlc_rows_body(
     const int16_t* __restrict__ levels, const int* __restrict__ meta,
     int mbw, const RowJob* __restrict__ jobs,
     uint32_t* __restrict__ stage,       // [row][item][kStageWordsPerItem]
@@ -323,10 +337,14 @@ __global__ void __launch_bounds__(1024) k_h264_cavlc_rows(
     int out_stride_words,
     int* __restrict__ out_bits) {       // [row]
   const RowJob job = jobs[blockIdx.x];
+  if constexpr (MONO) {
+    levels += (size_t)job.mb_base * kLevelsPerMb;
+    meta += (size_t)job.mb_base * kMetaPerMb;
+  }
   const int tid = threadIdx.x;
   const int NT = blockDim.x;   // 512 (many blocks: throughput regime)
                                // or 1024 (few blocks: latency regime)
-  const bool i_slice = (job.flags & 1) != 0;
+  const bool i_slice = (job.flags & kJobIdr) != 0;
   const int seg_mbw = job.seg_mbw;
   const size_t row_base = (size_t)job.mb_row * mbw + job.mbx0;
   const int nitems = items_per_row(seg_mbw);
@@ -345,7 +363,7 @@ __global__ void __launch_bounds__(1024) k_h264_cavlc_rows(
   __shared__ short s_skiprun[kMaxSegMbw];
   __shared__ int s_trailing;
   for (int mb = tid; mb < seg_mbw; mb += NT)
-    precompute_mb(levels, meta, row_base + mb, i_slice, &s_mb[mb]);
+    precompute_mb<MONO>(levels, meta, row_base + mb, i_slice, &s_mb[mb]);
   __syncthreads();
   if (tid == 0) {
     int run = 0;
@@ -372,6 +390,7 @@ __global__ void __launch_bounds__(1024) k_h264_cavlc_rows(
       bw.ue(job.first_mb);
       bw.ue(i_slice ? 7 : 5);
       bw.ue(0);
+      if constexpr (MONO) bw.u(job.plane, 2);   // colour_plane_id
       bw.u(job.frame_num & 0xFFFF, 16);
       if (i_slice) bw.ue(job.idr_pic_id);
       if (!i_slice) {
@@ -385,7 +404,8 @@ __global__ void __launch_bounds__(1024) k_h264_cavlc_rows(
         bw.u(0, 1);
       }
       bw.se(job.qp - 26);
-      bw.ue((job.flags & 2) ? 2 : 1);  // disable_deblocking_filter_idc
+      // disable_deblocking_filter_idc
+      bw.ue((job.flags & kJobDeblock) ? 2 : 1);
       bits = bw.flush();
     } else if (item == nitems - 1) {
       if (!i_slice && s_trailing > 0) bw.ue(s_trailing);
@@ -410,14 +430,18 @@ __global__ void __launch_bounds__(1024) k_h264_cavlc_rows(
           }
           bw.se(m.mvx - mvpx);
           bw.se(m.mvy - mvpy);
-          int cbp = (cbp_chroma << 4) | (MB_CBPL(m.flags) ? 15 : 0);
-          bw.ue(dev_inter_cbp_codenum(cbp));
-          if (cbp) bw.se(0);  // mb_qp_delta
+          if constexpr (MONO) {
+            bw.ue(0);  // coded_block_pattern 0, no mb_qp_delta
+          } else {
+            int cbp = (cbp_chroma << 4) | (MB_CBPL(m.flags) ? 15 : 0);
+            bw.ue(dev_inter_cbp_codenum(cbp));
+            if (cbp) bw.se(0);  // mb_qp_delta
+          }
         } else {
           int i16 = 1 + MB_LMODE(m.flags) + 4 * cbp_chroma +
                     12 * MB_CBPL(m.flags);
           bw.ue(i_slice ? i16 : 5 + i16);
-          bw.ue(MB_CMODE(m.flags));
+          if constexpr (!MONO) bw.ue(MB_CMODE(m.flags));
           bw.se(0);  // mb_qp_delta
         }
         bits = bw.flush();
@@ -449,6 +473,8 @@ __global__ void __launch_bounds__(1024) k_h264_cavlc_rows(
           }
           bits = bw.flush();
         }
+      } else if (MONO) {
+        // chroma slots 18..27: nothing in a monochrome picture
       } else if (slot < 20) {
         if (cbp_chroma > 0) {
           int comp = slot - 18;
@@ -541,6 +567,37 @@ __global__ void __launch_bounds__(1024) k_h264_cavlc_rows(
     if (shift && (w0 + nwords) <= last_dst)
       atomicOr(&row_out[w0 + nwords], carry);
   }
+}
+
+__global__ void __launch_bounds__(1024) k_h264_cavlc_rows(
+    const int16_t* __restrict__ levels, const int* __restrict__ meta,
+    int mbw, const RowJob* __restrict__ jobs, uint32_t* __restrict__ stage,
+    int* __restrict__ nbits, uint32_t* __restrict__ out,
+    int out_stride_words, int* __restrict__ out_bits) {
+  cavlc_rows_body<false>(levels, meta, mbw, jobs, stage, nbits, out,
+                         out_stride_words, out_bits);
+}
+
+__global__ void __launch_bounds__(1024) k_h264_cavlc_rows_mono(
+    const int16_t* __restrict__ levels, const int* __restrict__ meta,
+    int mbw, const RowJob* __restrict__ jobs, uint32_t* __restrict__ stage,
+    int* __restrict__ nbits, uint32_t* __restrict__ out,
+    int out_stride_words, int* __restrict__ out_bits) {
+  cavlc_rows_body<true>(levels, meta, mbw, jobs, stage, nbits, out,
+                        out_stride_words, out_bits);
+}
+
+void launch_h264_cavlc_mono(const int16_t* d_levels, const int* d_meta,
+                            int mbw, int n_jobs, const RowJob* d_jobs,
+                            uint32_t* d_stage, int* d_nbits, uint32_t* d_out,
+                            int out_stride_words, int* d_out_bits,
+                            hipStream_t stream) {
+  if (n_jobs == 0) return;
+  // same block-width rule as the 4:2:0 launch below
+  const int nt = n_jobs <= 256 ? 1024 : 512;
+  hipLaunchKernelGGL(k_h264_cavlc_rows_mono, dim3(n_jobs), dim3(nt), 0,
+                     stream, d_levels, d_meta, mbw, d_jobs, d_stage, d_nbits,
+                     d_out, out_stride_words, d_out_bits);
 }
 
 void launch_h264_cavlc(const int16_t* d_levels, const int* d_meta, int mbw,

@@ -6,6 +6,8 @@
 // reference: native/cpu/h264/deblock.h (byte-identical by tests).
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "h264_gpu_layout.h"
 #include "h264_kernels.h"
 
@@ -127,14 +129,25 @@ struct DbShared {
   DbInfo info[kMaxSegMbw];
 };
 
-__global__ __launch_bounds__(64) void k_h264_deblock(
+// A Hi444 separate colour plane is a monochrome picture: luma tile only.
+struct DbSharedMono {
+  uint8_t y[16][kMaxSegMbw * 16];
+  DbInfo info[kMaxSegMbw];
+};
+
+// One body, two kernels. MONO filters a monochrome picture: luma edges
+// only, no chroma tile or chroma lanes, curCb/curCr never dereferenced
+// (the mono kernel passes null). Its inter MBs carry no residual (the row
+// kernel re-codes those as I16x16), so nz stays 0 without reading levels
+// and bS 2 cannot occur.
+template <bool MONO>
+__device__ __forceinline__ void deblock_body(
     uint8_t* __restrict__ curY, uint8_t* __restrict__ curCb,
     uint8_t* __restrict__ curCr, int ypitch, int cpitch, int mbw,
-    const RowJob* __restrict__ jobs, const int16_t* __restrict__ levels,
+    const RowJob& job, const int16_t* __restrict__ levels,
     const int* __restrict__ meta) {
-  __shared__ DbShared sh;
-  const RowJob job = jobs[blockIdx.x];
-  if (job.flags & 1) {
+  __shared__ std::conditional_t<MONO, DbSharedMono, DbShared> sh;
+  if (job.flags & kJobIdr) {
     // IDR rows: all-intra, every edge is bS 3/4 — still filter
   }
   const int lane = threadIdx.x;
@@ -147,11 +160,13 @@ __global__ __launch_bounds__(64) void k_h264_deblock(
   for (int r = 0; r < 16; ++r)
     for (int x = lane; x < wpx; x += 64)
       sh.y[r][x] = curY[(size_t)(y0 + r) * ypitch + px0 + x];
-  for (int r = 0; r < 8; ++r)
-    for (int x = lane; x < cwpx; x += 64) {
-      sh.cb[r][x] = curCb[(size_t)(cy0 + r) * cpitch + cpx0 + x];
-      sh.cr[r][x] = curCr[(size_t)(cy0 + r) * cpitch + cpx0 + x];
-    }
+  if constexpr (!MONO) {
+    for (int r = 0; r < 8; ++r)
+      for (int x = lane; x < cwpx; x += 64) {
+        sh.cb[r][x] = curCb[(size_t)(cy0 + r) * cpitch + cpx0 + x];
+        sh.cr[r][x] = curCr[(size_t)(cy0 + r) * cpitch + cpx0 + x];
+      }
+  }
   // info: one lane per MB; nz from the levels buffer (inter AC blocks)
   for (int m = lane; m < segw; m += 64) {
     const size_t mb = (size_t)job.mb_row * mbw + job.mbx0 + m;
@@ -159,11 +174,11 @@ __global__ __launch_bounds__(64) void k_h264_deblock(
     const int m1 = meta[mb * kMetaPerMb + 1];
     const int mode = m0 & 3;
     DbInfo di;
-    di.intra = mode == kIntra || (job.flags & 1);
+    di.intra = mode == kIntra || (job.flags & kJobIdr);
     di.mvx = mode == kInter ? (int)(short)(m1 & 0xFFFF) : 0;
     di.mvy = mode == kInter ? (m1 >> 16) : 0;
     di.nz = 0;
-    if (mode == kInter) {
+    if (!MONO && mode == kInter) {
       const int16_t* lv = levels + mb * kLevelsPerMb + kLumaAcOff;
       for (int b = 0; b < 16; ++b) {
         int any = 0;
@@ -202,6 +217,8 @@ __global__ __launch_bounds__(64) void k_h264_deblock(
                          tc0);
           }
         }
+      } else if constexpr (MONO) {
+        // no chroma lanes
       } else if (lane < 32 && e < 2) {      // chroma vertical edge e
         if (!(e == 0 && m == 0)) {
           const int pl = (lane - 16) >> 3, yy = (lane - 16) & 7;
@@ -251,11 +268,42 @@ __global__ __launch_bounds__(64) void k_h264_deblock(
   for (int r = 0; r < 16; ++r)
     for (int x = lane; x < wpx; x += 64)
       curY[(size_t)(y0 + r) * ypitch + px0 + x] = sh.y[r][x];
-  for (int r = 0; r < 8; ++r)
-    for (int x = lane; x < cwpx; x += 64) {
-      curCb[(size_t)(cy0 + r) * cpitch + cpx0 + x] = sh.cb[r][x];
-      curCr[(size_t)(cy0 + r) * cpitch + cpx0 + x] = sh.cr[r][x];
-    }
+  if constexpr (!MONO) {
+    for (int r = 0; r < 8; ++r)
+      for (int x = lane; x < cwpx; x += 64) {
+        curCb[(size_t)(cy0 + r) * cpitch + cpx0 + x] = sh.cb[r][x];
+        curCr[(size_t)(cy0 + r) * cpitch + cpx0 + x] = sh.cr[r][x];
+      }
+  }
+}
+
+__global__ __launch_bounds__(64) void k_h264_deblock(
+    uint8_t* __restrict__ curY, uint8_t* __restrict__ curCb,
+    uint8_t* __restrict__ curCr, int ypitch, int cpitch, int mbw,
+    const RowJob* __restrict__ jobs, const int16_t* __restrict__ levels,
+    const int* __restrict__ meta) {
+  const RowJob job = jobs[blockIdx.x];
+  deblock_body<false>(curY, curCb, curCr, ypitch, cpitch, mbw, job, levels,
+                      meta);
+}
+
+// cur is plane 0; planes lie plane_stride bytes apart (same pitch). Each
+// job filters its own plane, with its plane's region of meta.
+__global__ __launch_bounds__(64) void k_h264_deblock_mono(
+    uint8_t* __restrict__ cur, size_t plane_stride, int pitch, int mbw,
+    const RowJob* __restrict__ jobs, const int* __restrict__ meta) {
+  const RowJob job = jobs[blockIdx.x];
+  deblock_body<true>(cur + (size_t)job.plane * plane_stride, nullptr,
+                     nullptr, pitch, 0, mbw, job, nullptr,
+                     meta + (size_t)job.mb_base * kMetaPerMb);
+}
+
+void launch_h264_deblock_mono(uint8_t* d_cur, size_t plane_stride, int pitch,
+                              int mbw, int n_jobs, const RowJob* d_jobs,
+                              const int* d_meta, hipStream_t stream) {
+  if (n_jobs == 0) return;
+  hipLaunchKernelGGL(k_h264_deblock_mono, dim3(n_jobs), dim3(64), 0, stream,
+                     d_cur, plane_stride, pitch, mbw, d_jobs, d_meta);
 }
 
 void launch_h264_deblock(uint8_t* d_curY, uint8_t* d_curCb,

@@ -36,7 +36,7 @@ enum MbMode : int { kSkip = 0, kInter = 1, kIntra = 2 };
 struct RowJob {
   int mb_row;      // absolute MB row in the frame
   int qp;          // luma QP for this slice
-  int flags;       // bit0: I slice (IDR)
+  int flags;       // kJobIdr | kJobDeblock | kJobMono
   int stripe_y0;   // stripe pixel bounds (for ME clamping)
   int stripe_y1;
   // slice-header fields for the GPU entropy kernel
@@ -45,7 +45,20 @@ struct RowJob {
   int idr_pic_id;
   int mbx0;        // first MB column of this segment
   int seg_mbw;     // segment width in MBs
+  // Hi444 separate colour planes (flags bit2: the slice is a monochrome
+  // picture). All zero for 4:2:0. Every other field stays plane-relative;
+  // the mono kernels add plane * plane_stride to their sample pointers
+  // and mb_base MBs to levels/meta.
+  int plane;       // colour_plane_id (0 Y, 1 Cb, 2 Cr)
+  int mb_base;     // MB index where this plane's levels/meta start
 };
+
+// RowJob::flags bits. kJobMono describes the job (a monochrome slice of
+// plane `plane`) to whoever reads the job list; no kernel branches on it,
+// the host launches the mono kernels for such jobs.
+constexpr int kJobIdr = 1;       // I slice (IDR)
+constexpr int kJobDeblock = 2;   // slice header signals deblocking idc 2
+constexpr int kJobMono = 4;
 
 // rows wider than this are split into ceil(mbw / kMaxSegMbw) slices
 constexpr int kMaxSegMbw = 128;

@@ -39,6 +39,26 @@ void launch_h264_deblock(uint8_t* d_curY, uint8_t* d_curCb,
                          const int16_t* d_levels, const int* d_meta,
                          hipStream_t stream);
 
+// Hi444 separate colour planes: every job is a monochrome slice of plane
+// job.plane. src/ref/cur point at plane 0 and the planes lie plane_stride
+// bytes apart with one pitch; levels/meta hold the planes back to back
+// (job.mb_base). One launch covers all three planes' jobs.
+void launch_h264_rows4_mono(const uint8_t* src, const uint8_t* ref,
+                            uint8_t* cur, size_t plane_stride, int pitch,
+                            int w, int h, int mbw, int n_jobs,
+                            const RowJob* d_jobs, int16_t* d_levels,
+                            int* d_meta, hipStream_t stream);
+
+void launch_h264_deblock_mono(uint8_t* d_cur, size_t plane_stride, int pitch,
+                              int mbw, int n_jobs, const RowJob* d_jobs,
+                              const int* d_meta, hipStream_t stream);
+
+void launch_h264_cavlc_mono(const int16_t* d_levels, const int* d_meta,
+                            int mbw, int n_jobs, const RowJob* d_jobs,
+                            uint32_t* d_stage, int* d_nbits, uint32_t* d_out,
+                            int out_stride_words, int* d_out_bits,
+                            hipStream_t stream);
+
 void launch_h264_cavlc(const int16_t* d_levels, const int* d_meta, int mbw,
                        int n_jobs, const RowJob* d_jobs, uint32_t* d_stage,
                        int* d_nbits, uint32_t* d_out, int out_stride_words,

@@ -670,7 +670,7 @@ __global__ void __launch_bounds__(128) k_h264_rows(
     int* __restrict__ meta) {
   const RowJob job = jobs[blockIdx.x];
   const int qp = job.qp;
-  const bool i_slice = (job.flags & 1) != 0;
+  const bool i_slice = (job.flags & kJobIdr) != 0;
   const int mby = job.mb_row;
   const int lane = threadIdx.x & 63;
 
@@ -696,7 +696,7 @@ __global__ void __launch_bounds__(64) k_h264_me(
   const RowJob job = jobs[job_idx];
   const int mbx = job.mbx0 + blockIdx.x % seg_max;
   if (blockIdx.x % seg_max >= job.seg_mbw) return;
-  if (job.flags & 1) return;  // I rows have no ME
+  if (job.flags & kJobIdr) return;  // I rows have no ME
   const int lane = threadIdx.x;
   const int mby = job.mb_row;
   const int x0 = mbx * 16, y0 = mby * 16;
@@ -844,7 +844,7 @@ __global__ void __launch_bounds__(64) k_h264_me_mfma(
   const RowJob job = jobs[job_idx];
   const int mbx = job.mbx0 + blockIdx.x % seg_max;
   if (blockIdx.x % seg_max >= job.seg_mbw) return;
-  if (job.flags & 1) return;
+  if (job.flags & kJobIdr) return;
   const int lane = threadIdx.x;
   const int mby = job.mb_row;
   const int x0 = mbx * 16, y0 = mby * 16;

@@ -19,6 +19,8 @@
 // to the CPU reference encoder) — enforced by tests/test_gpu_h264.py.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "h264_gpu_layout.h"
 #include "h264_kernels.h"
 #include "h264_rows_common.h"
@@ -37,15 +39,28 @@ struct Shared {
   uint8_t ccol[2][16];
 };
 
+// The monochrome kernel (one Hi444 colour plane per slice) adds one word
+// per luma wave: "this wave quantised a non-zero inter level".
+struct SharedMono : Shared {
+  int nz[4];
+};
+
 // ---- luma: wave w handles NP consecutive passes starting at w*NP ---------
-template <int NP>
+// MONO: the slice is a monochrome picture. A monochrome P macroblock can
+// only signal coded_block_pattern 0 here (cpu/h264/encoder.cpp,
+// encode_p16 returning false), so an inter MB whose quantised residual is
+// non-zero is re-coded as I16x16: the four waves OR their "any level"
+// bits through LDS behind one barrier and, on a hit, all fall through to
+// the intra path, which rewrites M[0] as intra and keeps the ME hint.
+template <int NP, bool MONO = false>
 __device__ void luma_wave(const uint8_t* __restrict__ srcY, int ypitch,
                           int w_, int h, const uint8_t* __restrict__ refY,
                           uint8_t* __restrict__ curY, int mbw, int mby,
                           int qp, bool i_slice,
                           const int16_t* __restrict__ levels_base,
                           int* __restrict__ meta, int lane, int w,
-                          int mbx0, int seg_mbw, Shared* sh) {
+                          int mbx0, int seg_mbw,
+                          std::conditional_t<MONO, SharedMono, Shared>* sh) {
   const int y0 = mby * 16;
   const int r = lane >> 2, cq = (lane & 3) * 4;
   const int g = lane >> 4, c = lane & 15;
@@ -136,28 +151,43 @@ __device__ void luma_wave(const uint8_t* __restrict__ srcY, int ypitch,
         lvl_p[pi] = lvl;
         store_lvl_pair(L + kLumaAcOff + blk * 16, c, lvl, lane);
       }
-      // recon: no cbp gate needed — zero levels dequantize to zero
+      bool recode_intra = false;
+      if constexpr (MONO) {
+        int any = 0;
 #pragma unroll
-      for (int pi = 0; pi < NP; ++pi) {
-        int pass = NP * w + pi;
-        int blk = pass * 4 + g;
-        int bx = blk & 3, by = blk >> 2;
-        int d = dequant_c(lvl_p[pi], qp, coeff_cls(c));
-        int rec = idct4_wave(d, lane);
-        int py = by * 4 + (c >> 2), px = bx * 4 + (c & 3);
-        int pix = clip8(rec + pred_at(py, px));
-        int p1 = __shfl(pix, lane + 1), p2 = __shfl(pix, lane + 2),
-            p3 = __shfl(pix, lane + 3);
-        if ((c & 3) == 0)
-          *reinterpret_cast<uint32_t*>(
-              curY + (size_t)(y0 + py) * ypitch + x0 + px) =
-              (uint32_t)pix | ((uint32_t)p1 << 8) | ((uint32_t)p2 << 16) |
-              ((uint32_t)p3 << 24);
-        if (px == 15) lcol_n[py] = (uint8_t)pix;
+        for (int pi = 0; pi < NP; ++pi) any |= lvl_p[pi] != 0;
+        const bool wave_any = __ballot(any) != 0;
+        if (lane == 0) sh->nz[w] = wave_any;
+        __syncthreads();
+        // uniform across the block: every wave reads the same four words
+        recode_intra = (sh->nz[0] | sh->nz[1] | sh->nz[2] | sh->nz[3]) != 0;
       }
-      __syncthreads();
-      have_left = true;
-      continue;
+      if (!recode_intra) {
+        // recon: no cbp gate needed — zero levels dequantize to zero
+#pragma unroll
+        for (int pi = 0; pi < NP; ++pi) {
+          int pass = NP * w + pi;
+          int blk = pass * 4 + g;
+          int bx = blk & 3, by = blk >> 2;
+          int d = dequant_c(lvl_p[pi], qp, coeff_cls(c));
+          int rec = idct4_wave(d, lane);
+          int py = by * 4 + (c >> 2), px = bx * 4 + (c & 3);
+          int pix = clip8(rec + pred_at(py, px));
+          int p1 = __shfl(pix, lane + 1), p2 = __shfl(pix, lane + 2),
+              p3 = __shfl(pix, lane + 3);
+          if ((c & 3) == 0)
+            *reinterpret_cast<uint32_t*>(
+                curY + (size_t)(y0 + py) * ypitch + x0 + px) =
+                (uint32_t)pix | ((uint32_t)p1 << 8) | ((uint32_t)p2 << 16) |
+                ((uint32_t)p3 << 24);
+          if (px == 15) lcol_n[py] = (uint8_t)pix;
+        }
+        __syncthreads();
+        have_left = true;
+        continue;
+      }
+      // MONO with a non-zero residual: fall through; the intra path
+      // overwrites every level the passes above stored
     }
 
     // ---- intra I16x16
@@ -426,7 +456,7 @@ __global__ void __launch_bounds__(384) k_h264_rows4(
     int* __restrict__ meta) {
   const RowJob job = jobs[blockIdx.x];
   const int qp = job.qp;
-  const bool i_slice = (job.flags & 1) != 0;
+  const bool i_slice = (job.flags & kJobIdr) != 0;
   const int mby = job.mb_row;
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -446,6 +476,41 @@ __global__ void __launch_bounds__(384) k_h264_rows4(
                        dev_chroma_qp(qp), i_slice, levels, meta, lane, 1,
                        job.mbx0, job.seg_mbw, &sh);
   }
+}
+
+// Monochrome variant for Hi444 separate colour planes: four luma waves,
+// no chroma waves. src/ref/cur are plane 0; planes lie plane_stride bytes
+// apart with the same pitch, and each job picks its own plane and its
+// plane's region of levels/meta.
+__global__ void __launch_bounds__(256) k_h264_rows4_mono(
+    const uint8_t* __restrict__ src, const uint8_t* __restrict__ ref,
+    uint8_t* __restrict__ cur, size_t plane_stride, int pitch, int w, int h,
+    int mbw, const RowJob* __restrict__ jobs, int16_t* __restrict__ levels,
+    int* __restrict__ meta) {
+  const RowJob job = jobs[blockIdx.x];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const size_t po = (size_t)job.plane * plane_stride;
+
+  __shared__ rows4::SharedMono sh;
+
+  rows4::luma_wave<1, true>(
+      src + po, pitch, w, h, ref + po, cur + po, mbw, job.mb_row, job.qp,
+      (job.flags & kJobIdr) != 0,
+      levels + (size_t)job.mb_base * kLevelsPerMb,
+      meta + (size_t)job.mb_base * kMetaPerMb, lane, wave, job.mbx0,
+      job.seg_mbw, &sh);
+}
+
+void launch_h264_rows4_mono(const uint8_t* src, const uint8_t* ref,
+                            uint8_t* cur, size_t plane_stride, int pitch,
+                            int w, int h, int mbw, int n_jobs,
+                            const RowJob* d_jobs, int16_t* d_levels,
+                            int* d_meta, hipStream_t stream) {
+  if (n_jobs == 0) return;
+  hipLaunchKernelGGL(k_h264_rows4_mono, dim3(n_jobs), dim3(256), 0, stream,
+                     src, ref, cur, plane_stride, pitch, w, h, mbw, d_jobs,
+                     d_levels, d_meta);
 }
 
 void launch_h264_rows4(const uint8_t* srcY, const uint8_t* srcCb,

@@ -617,7 +617,7 @@ PYBIND11_MODULE(_native, m) {
     }
     BenchPipeline(const std::string& kind, int width, int height, int qp_,
                   int stripe, int output_mode, int gpu_id,
-                  int pipeline_depth)
+                  int pipeline_depth, bool fullcolor)
         : w(width), h(height), qp(qp_), stripe_h(stripe) {
       CaptureSettings s;
       s.capture_width = w;
@@ -627,6 +627,7 @@ PYBIND11_MODULE(_native, m) {
       s.video_crf = qp;
       s.jpeg_quality = qp;
       s.gpu_id = gpu_id;
+      s.video_fullcolor = fullcolor;
       s.use_cpu = kind == "cpu";
       if (kind == "gpu") {
         p = make_hip_pipeline(s);
@@ -641,11 +642,11 @@ PYBIND11_MODULE(_native, m) {
   };
   py::class_<BenchPipeline>(m, "BenchPipeline")
       .def(py::init<const std::string&, int, int, int, int, int, int,
-                    int>(),
+                    int, bool>(),
            py::arg("kind"), py::arg("width"), py::arg("height"),
            py::arg("qp") = 28, py::arg("stripe_height") = 64,
            py::arg("output_mode") = 1, py::arg("gpu_id") = 0,
-           py::arg("pipeline_depth") = 1)
+           py::arg("pipeline_depth") = 1, py::arg("fullcolor") = false)
       .def_property_readonly("pipeline",
                              [](BenchPipeline& b) { return b.p->name(); })
       .def_readonly("last_frame_id", &BenchPipeline::last_frame_id)

@@ -4,6 +4,17 @@
 // independent bitstream with its own frame_num / recon region (SURVEY.md
 // §5.7 seam). HIPFLUX_CPU_ENTROPY=1 swaps the CAVLC kernel for the host
 // packer over D2H levels/meta.
+//
+// video_fullcolor: Hi444 (profile 244) with separate_colour_plane_flag=1,
+// the stream shape of the CPU StripeEncoder(fullcolor=true). Y, Cb and Cr
+// are three full-resolution planes laid back to back (one allocation each
+// for src/ref/cur, plane_stride_ bytes apart, cpitch_ == ypitch_), every
+// plane is coded as a monochrome picture by the mono kernels, and
+// levels/meta hold the planes back to back. Jobs run stripe -> plane ->
+// row -> segment, so one launch each of rows, deblock and CAVLC covers all
+// three planes and each stripe's slices come out plane-major. Motion
+// search runs per plane with that plane's pyramids. HIPFLUX_ROWS_V1 is
+// ignored in this mode: the 2-wave row kernel has no monochrome form.
 #include <cstdio>
 #include <cstdlib>
 
@@ -37,7 +48,8 @@ class HipH264Pipeline : public EncodePipeline {
   // compute of frame N+1 (x264-style frame pipelining; throughput mode).
   struct Out {
     std::vector<uint8_t> header;            // SPS/PPS on IDR
-    std::vector<std::vector<uint8_t>> rows;
+    std::vector<std::vector<uint8_t>> rows;   // slices, plane-major
+    int plane_slices = 0;                      // slices per colour plane
     std::vector<uint8_t> bytes;
     h264::GpuStripeParams p{};
     int y0 = 0, h = 0;
@@ -74,7 +86,7 @@ class HipH264Pipeline : public EncodePipeline {
     // it overlaps the PREVIOUS frame's entropy kernel + D2H on stream_
     HIP_CHECK(hipStreamWaitEvent(rows_stream_, ev_h2d_[par], 0));
     launch_bgrx_to_planes(d_frame_[par], w_, h_, frame.stride / 4, d_srcY_,
-                          d_srcCb_, d_srcCr_, ypitch_, cpitch_, false,
+                          d_srcCb_, d_srcCr_, ypitch_, cpitch_, fc_,
                           rows_stream_);
 
     // build row jobs for scheduled stripes (stripe stream state — IDR,
@@ -106,31 +118,47 @@ class HipH264Pipeline : public EncodePipeline {
       int rows = (std::min(st.y1, mbh_ * 16) - st.y0 + 15) / 16;
       // stripe's padded pixel bounds for ME clamping
       int sy0 = st.y0, sy1 = (row0 + rows) * 16;
-      for (int r = 0; r < rows; ++r) {
-        int x = 0;
-        for (int sg = 0; sg < segs_; ++sg) {
-          int segw = std::min(seg_w0_, mbw_ - x);
-          h_jobs_[par][n_jobs].mb_row = row0 + r;
-          h_jobs_[par][n_jobs].qp = qp;
-          h_jobs_[par][n_jobs].flags =
-              (sj.idr ? 1 : 0) | (settings_.video_deblock ? 2 : 0);
-          h_jobs_[par][n_jobs].stripe_y0 = sy0;
-          h_jobs_[par][n_jobs].stripe_y1 = sy1;
-          h_jobs_[par][n_jobs].first_mb = r * mbw_ + x;
-          h_jobs_[par][n_jobs].frame_num = static_cast<int>(sj.frame_num);
-          h_jobs_[par][n_jobs].idr_pic_id = static_cast<int>(sj.idr_pic_id);
-          h_jobs_[par][n_jobs].mbx0 = x;
-          h_jobs_[par][n_jobs].seg_mbw = segw;
-          x += segw;
-          ++n_jobs;
+      // planes outermost: a stripe's slices come out plane-major
+      for (int pl = 0; pl < planes_; ++pl) {
+        for (int r = 0; r < rows; ++r) {
+          int x = 0;
+          for (int sg = 0; sg < segs_; ++sg) {
+            int segw = std::min(seg_w0_, mbw_ - x);
+            h_jobs_[par][n_jobs].mb_row = row0 + r;
+            h_jobs_[par][n_jobs].qp = qp;
+            h_jobs_[par][n_jobs].flags =
+                (sj.idr ? h264gpu::kJobIdr : 0) |
+                (settings_.video_deblock ? h264gpu::kJobDeblock : 0) |
+                (fc_ ? h264gpu::kJobMono : 0);
+            h_jobs_[par][n_jobs].plane = pl;
+            h_jobs_[par][n_jobs].mb_base = pl * mbw_ * mbh_;
+            h_jobs_[par][n_jobs].stripe_y0 = sy0;
+            h_jobs_[par][n_jobs].stripe_y1 = sy1;
+            h_jobs_[par][n_jobs].first_mb = r * mbw_ + x;
+            h_jobs_[par][n_jobs].frame_num = static_cast<int>(sj.frame_num);
+            h_jobs_[par][n_jobs].idr_pic_id = static_cast<int>(sj.idr_pic_id);
+            h_jobs_[par][n_jobs].mbx0 = x;
+            h_jobs_[par][n_jobs].seg_mbw = segw;
+            x += segw;
+            ++n_jobs;
+          }
         }
       }
     }
     if (n_jobs == 0) return Pending{};
     parity_ ^= 1;
 
+    // fullcolor: the motion search runs once per plane, so it gets the
+    // same jobs again grouped by plane, behind the first n_jobs
+    const int me_jobs = n_jobs / planes_;
+    if (fc_) {
+      int at[3] = {n_jobs, n_jobs + me_jobs, n_jobs + 2 * me_jobs};
+      for (int j = 0; j < n_jobs; ++j)
+        h_jobs_[par][at[h_jobs_[par][j].plane]++] = h_jobs_[par][j];
+    }
     HIP_CHECK(hipMemcpyAsync(d_jobs_[par], h_jobs_[par],
-                             sizeof(h264gpu::RowJob) * n_jobs,
+                             sizeof(h264gpu::RowJob) * n_jobs *
+                                 (fc_ ? 2 : 1),
                              hipMemcpyHostToDevice, rows_stream_));
     // meta carries cross-frame tracking state (prev MV hints, hopeless
     // bits); seed this parity's buffer from the previous one so the
@@ -138,22 +166,31 @@ class HipH264Pipeline : public EncodePipeline {
     // damage-skipped stripes
     HIP_CHECK(hipMemcpyAsync(d_meta_[par], d_meta_[par ^ 1], meta_bytes_,
                              hipMemcpyDeviceToDevice, rows_stream_));
-    // luma pyramid (quarter res) for ME acquisition
-    if (!ctx.idr) {
-      h264gpu::launch_downsample2(d_srcY_, ypitch_, ypitch_, mbh_ * 16,
-                                  d_mip1_, ypitch_ / 2, rows_stream_);
-      h264gpu::launch_downsample2(d_mip1_, ypitch_ / 2, ypitch_ / 2,
-                                  mbh_ * 8, d_srcY2_, ypitch_ / 4,
-                                  rows_stream_);
-      h264gpu::launch_downsample2(d_refY_, ypitch_, ypitch_, mbh_ * 16,
-                                  d_mip1_, ypitch_ / 2, rows_stream_);
-      h264gpu::launch_downsample2(d_mip1_, ypitch_ / 2, ypitch_ / 2,
-                                  mbh_ * 8, d_refY2_, ypitch_ / 4,
-                                  rows_stream_);
+    // luma pyramid (quarter res) for ME acquisition; fullcolor: each
+    // plane searches on its own, with its own pyramids, as the CPU
+    // encoder's three plane encoders do
+    for (int pl = 0; pl < planes_; ++pl) {
+      const uint8_t* src = d_srcY_ + pl * plane_stride_;
+      const uint8_t* ref = d_refY_ + pl * plane_stride_;
+      uint8_t* src2 = d_srcY2_ + pl * pyr_stride_;
+      uint8_t* ref2 = d_refY2_ + pl * pyr_stride_;
+      if (!ctx.idr) {
+        h264gpu::launch_downsample2(src, ypitch_, ypitch_, mbh_ * 16,
+                                    d_mip1_, ypitch_ / 2, rows_stream_);
+        h264gpu::launch_downsample2(d_mip1_, ypitch_ / 2, ypitch_ / 2,
+                                    mbh_ * 8, src2, ypitch_ / 4,
+                                    rows_stream_);
+        h264gpu::launch_downsample2(ref, ypitch_, ypitch_, mbh_ * 16,
+                                    d_mip1_, ypitch_ / 2, rows_stream_);
+        h264gpu::launch_downsample2(d_mip1_, ypitch_ / 2, ypitch_ / 2,
+                                    mbh_ * 8, ref2, ypitch_ / 4,
+                                    rows_stream_);
+      }
+      h264gpu::launch_h264_me(
+          src, ypitch_, w_, h_, ref, src2, ref2, ypitch_ / 4, mbw_, me_jobs,
+          d_jobs_[par] + (fc_ ? n_jobs + pl * me_jobs : 0),
+          d_meta_[par] + pl * n_mb_ * h264gpu::kMetaPerMb, rows_stream_);
     }
-    h264gpu::launch_h264_me(d_srcY_, ypitch_, w_, h_, d_refY_, d_srcY2_,
-                            d_refY2_, ypitch_ / 4, mbw_, n_jobs,
-                            d_jobs_[par], d_meta_[par], rows_stream_);
 
     // One launch for all rows: the row kernel's cost is per-row LATENCY
     // (all rows run concurrently), so splitting into sequential batches
@@ -161,24 +198,32 @@ class HipH264Pipeline : public EncodePipeline {
     // Entropy overlap is cross-FRAME instead (depth-2 pipelining).
     // 4-wave row kernel by default (issue-rate-bound chain split across
     // waves); HIPFLUX_ROWS_V1=1 falls back to the 2-wave variant
-    (rows_v1_ ? h264gpu::launch_h264_rows : h264gpu::launch_h264_rows4)(
-        d_srcY_, d_srcCb_, d_srcCr_, ypitch_, cpitch_, w_, h_, d_refY_,
-        d_refCb_, d_refCr_, d_curY_, d_curCb_, d_curCr_, mbw_, n_jobs,
-        d_jobs_[par], d_levels_[par], d_meta_[par], rows_stream_);
+    if (fc_)
+      h264gpu::launch_h264_rows4_mono(
+          d_srcY_, d_refY_, d_curY_, plane_stride_, ypitch_, w_, h_, mbw_,
+          n_jobs, d_jobs_[par], d_levels_[par], d_meta_[par], rows_stream_);
+    else
+      (rows_v1_ ? h264gpu::launch_h264_rows : h264gpu::launch_h264_rows4)(
+          d_srcY_, d_srcCb_, d_srcCr_, ypitch_, cpitch_, w_, h_, d_refY_,
+          d_refCb_, d_refCr_, d_curY_, d_curCb_, d_curCr_, mbw_, n_jobs,
+          d_jobs_[par], d_levels_[par], d_meta_[par], rows_stream_);
     if (cpu_entropy_) {
-      // the MB rows the jobs span, for the host packer
+      // the MB rows the jobs span, for the host packer (the same rows of
+      // every plane)
       const int row0 = h_jobs_[par][0].mb_row;
       const int rows = h_jobs_[par][n_jobs - 1].mb_row + 1 - row0;
       const size_t lvl_row = static_cast<size_t>(mbw_) * h264gpu::kLevelsPerMb;
       const size_t meta_row = static_cast<size_t>(mbw_) * h264gpu::kMetaPerMb;
-      HIP_CHECK(hipMemcpyAsync(h_levels_ + row0 * lvl_row,
-                               d_levels_[par] + row0 * lvl_row,
-                               rows * lvl_row * sizeof(int16_t),
-                               hipMemcpyDeviceToHost, rows_stream_));
-      HIP_CHECK(hipMemcpyAsync(h_meta_ + row0 * meta_row,
-                               d_meta_[par] + row0 * meta_row,
-                               rows * meta_row * sizeof(int),
-                               hipMemcpyDeviceToHost, rows_stream_));
+      for (int pl = 0; pl < planes_; ++pl) {
+        const size_t lo = (static_cast<size_t>(pl) * mbh_ + row0) * lvl_row;
+        const size_t mo = (static_cast<size_t>(pl) * mbh_ + row0) * meta_row;
+        HIP_CHECK(hipMemcpyAsync(h_levels_ + lo, d_levels_[par] + lo,
+                                 rows * lvl_row * sizeof(int16_t),
+                                 hipMemcpyDeviceToHost, rows_stream_));
+        HIP_CHECK(hipMemcpyAsync(h_meta_ + mo, d_meta_[par] + mo,
+                                 rows * meta_row * sizeof(int),
+                                 hipMemcpyDeviceToHost, rows_stream_));
+      }
     }
     HIP_CHECK(hipEventRecord(ev_rows_[par], rows_stream_));
     // in-loop deblock of the current recon (within-slice edges only;
@@ -189,10 +234,15 @@ class HipH264Pipeline : public EncodePipeline {
     // below join both streams before the recon becomes the reference.
     if (settings_.video_deblock) {
       HIP_CHECK(hipStreamWaitEvent(db_stream_, ev_rows_[par], 0));
-      h264gpu::launch_h264_deblock(d_curY_, d_curCb_, d_curCr_, ypitch_,
-                                   cpitch_, mbw_, n_jobs, d_jobs_[par],
-                                   d_levels_[par], d_meta_[par],
-                                   db_stream_);
+      if (fc_)
+        h264gpu::launch_h264_deblock_mono(d_curY_, plane_stride_, ypitch_,
+                                          mbw_, n_jobs, d_jobs_[par],
+                                          d_meta_[par], db_stream_);
+      else
+        h264gpu::launch_h264_deblock(d_curY_, d_curCb_, d_curCr_, ypitch_,
+                                     cpitch_, mbw_, n_jobs, d_jobs_[par],
+                                     d_levels_[par], d_meta_[par],
+                                     db_stream_);
       HIP_CHECK(hipEventRecord(ev_db_[par], db_stream_));
     }
     int copy_words = 0;
@@ -200,10 +250,10 @@ class HipH264Pipeline : public EncodePipeline {
       // entropy rides stream_ so the NEXT frame's produce chain on
       // rows_stream_ overlaps it (levels/meta are parity-buffered)
       HIP_CHECK(hipStreamWaitEvent(stream_, ev_rows_[par], 0));
-      h264gpu::launch_h264_cavlc(d_levels_[par], d_meta_[par], mbw_,
-                                 n_jobs, d_jobs_[par], d_stage_, d_nbits_,
-                                 d_entout_[par], ent_stride_words_,
-                                 d_outbits_[par], stream_);
+      (fc_ ? h264gpu::launch_h264_cavlc_mono : h264gpu::launch_h264_cavlc)(
+          d_levels_[par], d_meta_[par], mbw_, n_jobs, d_jobs_[par], d_stage_,
+          d_nbits_, d_entout_[par], ent_stride_words_, d_outbits_[par],
+          stream_);
       // compaction: copy only ~the used prefix of each row's bitstream
       // (adaptive cap = 2x last frame's max row, full stride first frame;
       // rows that overflow the cap are re-copied exactly in collect)
@@ -225,8 +275,13 @@ class HipH264Pipeline : public EncodePipeline {
         if (span_y0 < 0) return;
         int rows16 = (std::min(span_y1, mbh_ * 16) - span_y0 + 15) / 16;
         copy_region(d_refY_, d_curY_, ypitch_, span_y0, rows16 * 16);
-        copy_region(d_refCb_, d_curCb_, cpitch_, span_y0 / 2, rows16 * 8);
-        copy_region(d_refCr_, d_curCr_, cpitch_, span_y0 / 2, rows16 * 8);
+        if (fc_) {   // three full-size planes
+          copy_region(d_refCb_, d_curCb_, ypitch_, span_y0, rows16 * 16);
+          copy_region(d_refCr_, d_curCr_, ypitch_, span_y0, rows16 * 16);
+        } else {
+          copy_region(d_refCb_, d_curCb_, cpitch_, span_y0 / 2, rows16 * 8);
+          copy_region(d_refCr_, d_curCr_, cpitch_, span_y0 / 2, rows16 * 8);
+        }
         span_y0 = span_y1 = -1;
       };
       for (const auto& sj : sjobs) {
@@ -276,13 +331,20 @@ class HipH264Pipeline : public EncodePipeline {
         p.deblock = settings_.video_deblock;
         p.frame_num = sj.frame_num;
         p.idr_pic_id = sj.idr_pic_id;
-        o.rows.resize(p.n_mb_rows * segs_);
+        o.plane_slices = p.n_mb_rows * segs_;
+        o.rows.resize(o.plane_slices * planes_);
         if (p.idr) {
-          h264::write_sps_nal(o.header, (p.width + 15) / 16,
-                              p.n_mb_rows, p.width, p.height);
+          const int smbw = (p.width + 15) / 16;
+          if (fc_)
+            h264::write_sps_444(o.header, smbw, p.n_mb_rows, p.width,
+                                p.height,
+                                h264::level_idc_for(smbw, p.n_mb_rows));
+          else
+            h264::write_sps_nal(o.header, smbw, p.n_mb_rows, p.width,
+                                p.height);
           h264::write_pps_nal(o.header);
         }
-        for (int r = 0; r < p.n_mb_rows * segs_; ++r)
+        for (int r = 0; r < o.plane_slices * planes_; ++r)
           pd.job_map[j++] = {int(i), r};
       }
     }
@@ -300,12 +362,19 @@ class HipH264Pipeline : public EncodePipeline {
       for (int j = 0; j < pd.n_jobs; ++j) {
         auto [si, sl] = pd.job_map[j];
         auto* dst = &pd.outs[si].rows[sl];
-        const h264::GpuStripeParams* pp = &pd.outs[si].p;
-        int r = sl / segs_;
+        // the stripe's parameters, pointed at this slice's plane
+        h264::GpuStripeParams pp = pd.outs[si].p;
+        if (fc_) {
+          pp.colour_plane = h_jobs_[par][j].plane;
+          pp.mb_base = static_cast<size_t>(h_jobs_[par][j].mb_base);
+        }
+        const int psl = sl % pd.outs[si].plane_slices;
+        int r = psl / segs_;
         int mbx0 = h_jobs_[par][j].mbx0, segw = h_jobs_[par][j].seg_mbw;
-        bool long_sc = sl == 0;
+        // 4-byte start code on the first slice of each plane
+        bool long_sc = psl == 0;
         pool_.submit([pp, r, mbx0, segw, long_sc, dst] {
-          h264::encode_seg_nal_from_gpu(*pp, r, mbx0, segw, long_sc, *dst);
+          h264::encode_seg_nal_from_gpu(pp, r, mbx0, segw, long_sc, *dst);
         });
       }
       pool_.wait_all();
@@ -329,8 +398,8 @@ class HipH264Pipeline : public EncodePipeline {
             auto [si, sl] = pd.job_map[j];
             h264::assemble_gpu_row_nal(
                 h_entout_[par] + (size_t)j * ent_stride_words_,
-                h_outbits_[par][j], pd.outs[si].idr, sl == 0,
-                pd.outs[si].rows[sl]);
+                h_outbits_[par][j], pd.outs[si].idr,
+                sl % pd.outs[si].plane_slices == 0, pd.outs[si].rows[sl]);
           }
         });
       }
@@ -442,7 +511,7 @@ class HipH264Pipeline : public EncodePipeline {
     d.ypitch = ypitch_;
     d.cpitch = cpitch_;
     size_t ysz = static_cast<size_t>(ypitch_) * mbh_ * 16;
-    size_t csz = static_cast<size_t>(cpitch_) * mbh_ * 8;
+    size_t csz = fc_ ? ysz : static_cast<size_t>(cpitch_) * mbh_ * 8;
     d.y.resize(ysz);
     d.cb.resize(csz);
     d.cr.resize(csz);
@@ -450,8 +519,9 @@ class HipH264Pipeline : public EncodePipeline {
     HIP_CHECK(hipMemcpy(d.y.data(), d_refY_, ysz, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(d.cb.data(), d_refCb_, csz, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(d.cr.data(), d_refCr_, csz, hipMemcpyDeviceToHost));
-    size_t nlv = static_cast<size_t>(mbw_) * mbh_ * h264gpu::kLevelsPerMb;
-    size_t nmt = static_cast<size_t>(mbw_) * mbh_ * h264gpu::kMetaPerMb;
+    // fullcolor: plane-major (all of Y, then Cb, then Cr)
+    size_t nlv = n_mb_ * planes_ * h264gpu::kLevelsPerMb;
+    size_t nmt = n_mb_ * planes_ * h264gpu::kMetaPerMb;
     d.levels.resize(nlv);
     d.meta.resize(nmt);
     const int last_par = parity_ ^ 1;
@@ -492,21 +562,38 @@ class HipH264Pipeline : public EncodePipeline {
     mbw_ = (w + 15) / 16;
     mbh_ = (h + 15) / 16;
     ypitch_ = mbw_ * 16;
-    cpitch_ = mbw_ * 8;
+    cpitch_ = fc_ ? ypitch_ : mbw_ * 8;
     const size_t ysz = static_cast<size_t>(ypitch_) * mbh_ * 16;
     const size_t csz = static_cast<size_t>(cpitch_) * mbh_ * 8;
     for (int i = 0; i < 2; ++i)
       arena_.dev(d_frame_[i], static_cast<size_t>(w) * h * 4);
-    arena_.dev(d_srcY_, ysz);
-    arena_.dev(d_srcCb_, csz);
-    arena_.dev(d_srcCr_, csz);
-    arena_.dev(d_refY_, ysz);
-    arena_.dev(d_refCb_, csz);
-    arena_.dev(d_refCr_, csz);
-    arena_.dev(d_curY_, ysz);
-    arena_.dev(d_curCb_, csz);
-    arena_.dev(d_curCr_, csz);
-    const size_t n_mb = static_cast<size_t>(mbw_) * mbh_;
+    plane_stride_ = fc_ ? ysz : 0;
+    if (fc_) {
+      // three full-size planes back to back: the mono kernels reach
+      // plane p at base + p * plane_stride_
+      arena_.dev(d_srcY_, 3 * ysz);
+      arena_.dev(d_refY_, 3 * ysz);
+      arena_.dev(d_curY_, 3 * ysz);
+      d_srcCb_ = d_srcY_ + ysz;
+      d_srcCr_ = d_srcY_ + 2 * ysz;
+      d_refCb_ = d_refY_ + ysz;
+      d_refCr_ = d_refY_ + 2 * ysz;
+      d_curCb_ = d_curY_ + ysz;
+      d_curCr_ = d_curY_ + 2 * ysz;
+    } else {
+      arena_.dev(d_srcY_, ysz);
+      arena_.dev(d_srcCb_, csz);
+      arena_.dev(d_srcCr_, csz);
+      arena_.dev(d_refY_, ysz);
+      arena_.dev(d_refCb_, csz);
+      arena_.dev(d_refCr_, csz);
+      arena_.dev(d_curY_, ysz);
+      arena_.dev(d_curCb_, csz);
+      arena_.dev(d_curCr_, csz);
+    }
+    n_mb_ = static_cast<size_t>(mbw_) * mbh_;
+    // levels/meta: one region per coded plane, back to back
+    const size_t n_mb = n_mb_ * planes_;
     meta_bytes_ = n_mb * h264gpu::kMetaPerMb * sizeof(int);
     for (int i = 0; i < 2; ++i) {
       arena_.dev(d_levels_[i], n_mb * h264gpu::kLevelsPerMb);
@@ -516,14 +603,15 @@ class HipH264Pipeline : public EncodePipeline {
       HIP_CHECK(hipMemset(d_meta_[i], 0, meta_bytes_));
     }
     arena_.dev(d_mip1_, static_cast<size_t>(ypitch_ / 2) * mbh_ * 8);
-    arena_.dev(d_srcY2_, static_cast<size_t>(ypitch_ / 4) * mbh_ * 4);
-    arena_.dev(d_refY2_, static_cast<size_t>(ypitch_ / 4) * mbh_ * 4);
+    pyr_stride_ = static_cast<size_t>(ypitch_ / 4) * mbh_ * 4;
+    arena_.dev(d_srcY2_, pyr_stride_ * planes_);
+    arena_.dev(d_refY2_, pyr_stride_ * planes_);
     const char* segs_env = std::getenv("HIPFLUX_SEGS");
-    const h264::SegPlan plan =
-        h264::seg_plan(mbw_, mbh_, segs_env ? std::atoi(segs_env) : 0);
+    const h264::SegPlan plan = h264::seg_plan(
+        mbw_, mbh_, segs_env ? std::atoi(segs_env) : 0, planes_);
     segs_ = plan.segs;
     seg_w0_ = plan.widest;
-    const size_t max_jobs = static_cast<size_t>(mbh_) * segs_;
+    const size_t max_jobs = static_cast<size_t>(mbh_) * segs_ * planes_;
     arena_.pinned(h_levels_, n_mb * h264gpu::kLevelsPerMb);
     arena_.pinned(h_meta_, n_mb * h264gpu::kMetaPerMb);
     // GPU entropy buffers (one slot per SLICE = row segment)
@@ -536,10 +624,11 @@ class HipH264Pipeline : public EncodePipeline {
     arena_.dev(d_stage_, max_jobs * ent_stride_words_);
     arena_.dev(d_nbits_, max_jobs * nitems);
     for (int i = 0; i < 2; ++i) {
-      arena_.dev(d_jobs_[i], max_jobs);
+      // fullcolor keeps a second, plane-grouped copy for the motion search
+      arena_.dev(d_jobs_[i], max_jobs * (fc_ ? 2 : 1));
       arena_.dev(d_entout_[i], max_jobs * ent_stride_words_);
       arena_.dev(d_outbits_[i], max_jobs);
-      arena_.pinned(h_jobs_[i], max_jobs);
+      arena_.pinned(h_jobs_[i], max_jobs * (fc_ ? 2 : 1));
       arena_.pinned(h_entout_[i], max_jobs * ent_stride_words_);
       arena_.pinned(h_outbits_[i], max_jobs);
     }
@@ -557,6 +646,12 @@ class HipH264Pipeline : public EncodePipeline {
   Event ev_done_[2], ev_h2d_[2], ev_rows_[2], ev_db_[2];
   CompactReadback<uint32_t> readback_;   // bitstream words per slice
   int stripe_h_ = 64;
+  // Hi444 separate colour planes: three monochrome pictures per frame
+  const bool fc_ = settings_.video_fullcolor;
+  const int planes_ = fc_ ? 3 : 1;
+  size_t plane_stride_ = 0;   // bytes between the planes of src/ref/cur
+  size_t pyr_stride_ = 0;     // ... of the quarter-res pyramids
+  size_t n_mb_ = 0;           // MBs per plane
   int w_ = 0, h_ = 0, mbw_ = 0, mbh_ = 0, ypitch_ = 0, cpitch_ = 0;
   int segs_ = 1, seg_w0_ = 0;     // slices per MB row, widest segment
   uint8_t* d_frame_[2] = {nullptr, nullptr};
