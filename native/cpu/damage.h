@@ -4,6 +4,7 @@
 // "damage-gated encoders are application-limited", webrtc_mode.py:2186).
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -19,6 +20,12 @@ class DamageTracker {
   // duration: frames a block stays damaged after its last change.
   void update(const uint8_t* cur, int stride, int threshold, int duration);
 
+  // The same age / still-frame update from a block diff done elsewhere
+  // (the device front end): flags holds blocks_x() * blocks_y() bytes,
+  // nonzero = the block changed; null = everything changed (the first
+  // frame after a reset). Keeps no copy of the frame.
+  void apply_dirty(const uint8_t* flags, int duration);
+
   // True if any block intersecting rows [y0, y1) is currently damaged.
   bool stripe_damaged(int y0, int y1) const;
   bool any_damaged() const;
@@ -29,6 +36,10 @@ class DamageTracker {
   const std::vector<uint16_t>& ages() const { return age_; }
 
  private:
+  void mark_all(int duration);
+  // ages block i; returns dirty
+  bool age_block(std::size_t i, bool dirty, int duration);
+
   int w_ = 0, h_ = 0, block_ = 16, bx_ = 0, by_ = 0;
   std::vector<uint8_t> prev_;
   std::vector<uint16_t> age_;

@@ -40,6 +40,47 @@ inline void box_downscale_bgrx(const uint8_t* src, int sstride, int w,
   }
 }
 
+// Output size of the fractional bilinear downscale along one axis.
+inline int bilinear_out_size(int n, float scale) {
+  return std::max(1, static_cast<int>(n * scale + 0.5f));
+}
+
+// Per-axis sample table of the fractional bilinear downscale: output
+// sample i reads source samples idx[i] and idx[i] + 1 (idx[i] alone when
+// n_in == 1) with the 8-bit weight wt[i] on the second. Source position of
+// output sample center i: (i + 0.5) / scale - 0.5, in 16.16 fixed point
+// computed from the integer output size. The device front end uploads
+// these tables, so the 64-bit position math and the clamps exist once.
+inline void bilinear_axis_table(int n_in, int n_out, std::vector<int>& idx,
+                                std::vector<int>& wt) {
+  const int64_t step = (static_cast<int64_t>(n_in) << 16) / n_out;
+  idx.resize(n_out);
+  wt.resize(n_out);
+  for (int i = 0; i < n_out; ++i) {
+    int64_t s = ((2 * static_cast<int64_t>(i) + 1) * step - (1 << 16)) / 2;
+    if (s < 0) s = 0;
+    int ii = static_cast<int>(s >> 16);
+    if (ii > n_in - 2) ii = n_in - 2;
+    int fr = static_cast<int>((s >> 8) & 0xFF);
+    if (n_in == 1) { ii = 0; fr = 0; }
+    idx[i] = ii;
+    wt[i] = fr;
+  }
+}
+
+// One channel of one output pixel: a b / c e are the 2x2 source samples,
+// fx and fy the 8-bit weights. 8.8 horizontally, 8.16 vertically,
+// round-half-up.
+#if defined(__HIP__)
+__host__ __device__
+#endif
+inline uint8_t bilinear_sample(int a, int b, int c, int e, int fx, int fy) {
+  int top = (a << 8) + (b - a) * fx;       // 8.8
+  int bot = (c << 8) + (e - c) * fx;
+  int v = (top << 8) + (bot - top) * fy;   // 8.16
+  return static_cast<uint8_t>((v + (1 << 15)) >> 16);
+}
+
 // Fractional bilinear downscale (0 < scale < 1), fixed-point 16.16
 // sample positions with 8-bit interpolation weights. The reference's
 // `scale` knob (Wayland logical->pixel ratios like 1.5x) needs
@@ -49,34 +90,16 @@ inline void bilinear_downscale_bgrx(const uint8_t* src, int sstride, int w,
                                     int h, float scale,
                                     std::vector<uint8_t>& out, int& ow,
                                     int& oh, int& ostride) {
-  ow = std::max(1, static_cast<int>(w * scale + 0.5f));
-  oh = std::max(1, static_cast<int>(h * scale + 0.5f));
+  ow = bilinear_out_size(w, scale);
+  oh = bilinear_out_size(h, scale);
   ostride = ow * 4;
   out.resize(static_cast<size_t>(ostride) * oh);
-  // source position of output pixel center i: (i + 0.5) / scale - 0.5,
-  // in 16.16 fixed point computed from the integer output size
-  const int64_t xstep = (static_cast<int64_t>(w) << 16) / ow;
-  const int64_t ystep = (static_cast<int64_t>(h) << 16) / oh;
-  std::vector<int> xi(ow);
-  std::vector<int> xw(ow);
-  for (int x = 0; x < ow; ++x) {
-    int64_t sx = ((2 * static_cast<int64_t>(x) + 1) * xstep - (1 << 16)) / 2;
-    if (sx < 0) sx = 0;
-    int ix = static_cast<int>(sx >> 16);
-    if (ix > w - 2) ix = w - 2;
-    int fr = static_cast<int>((sx >> 8) & 0xFF);
-    if (w == 1) { ix = 0; fr = 0; }
-    xi[x] = ix;
-    xw[x] = fr;
-  }
+  std::vector<int> xi, xw, yi, yw;
+  bilinear_axis_table(w, ow, xi, xw);
+  bilinear_axis_table(h, oh, yi, yw);
   for (int y = 0; y < oh; ++y) {
-    int64_t sy = ((2 * static_cast<int64_t>(y) + 1) * ystep - (1 << 16)) / 2;
-    if (sy < 0) sy = 0;
-    int iy = static_cast<int>(sy >> 16);
-    if (iy > h - 2) iy = h - 2;
-    int fy = static_cast<int>((sy >> 8) & 0xFF);
-    if (h == 1) { iy = 0; fy = 0; }
-    const uint8_t* r0 = src + static_cast<size_t>(iy) * sstride;
+    const int fy = yw[y];
+    const uint8_t* r0 = src + static_cast<size_t>(yi[y]) * sstride;
     const uint8_t* r1 = r0 + (h > 1 ? sstride : 0);
     uint8_t* d = out.data() + static_cast<size_t>(y) * ostride;
     for (int x = 0; x < ow; ++x) {
@@ -85,12 +108,8 @@ inline void bilinear_downscale_bgrx(const uint8_t* src, int sstride, int w,
       const uint8_t* c = r1 + static_cast<size_t>(xi[x]) * 4;
       const uint8_t* e = c + (w > 1 ? 4 : 0);
       const int fx = xw[x];
-      for (int ch = 0; ch < 4; ++ch) {
-        int top = (a[ch] << 8) + (b[ch] - a[ch]) * fx;       // 8.8
-        int bot = (c[ch] << 8) + (e[ch] - c[ch]) * fx;
-        int v = (top << 8) + (bot - top) * fy;               // 8.16
-        d[x * 4 + ch] = static_cast<uint8_t>((v + (1 << 15)) >> 16);
-      }
+      for (int ch = 0; ch < 4; ++ch)
+        d[x * 4 + ch] = bilinear_sample(a[ch], b[ch], c[ch], e[ch], fx, fy);
     }
   }
 }

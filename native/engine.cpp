@@ -1,6 +1,8 @@
 #include "engine.h"
 
+#include "cpu/overlay.h"
 #include "cpu/scale.h"
+#include "frontend_hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -39,79 +41,6 @@ void ScreenCapture::update_capture_region(int x, int y, int w, int h) {
   region_[0] = x; region_[1] = y; region_[2] = w; region_[3] = h;
   region_changed_.store(true);
 }
-
-namespace {
-
-inline uint8_t clip8u(long v) {
-  return static_cast<uint8_t>(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
-
-// Watermark: raw ".bgra" file = u32 width, u32 height, then BGRA pixels.
-// (The Python layer converts PNG -> .bgra via PIL; keeps libpng out of the
-// native build.) Locations: 1=TL 2=TR 3=BL 4=BR 5=center 6=animated.
-struct Watermark {
-  int w = 0, h = 0;
-  std::vector<uint8_t> bgra;
-  bool load(const std::string& path) {
-    FILE* f = std::fopen(path.c_str(), "rb");
-    if (!f) return false;
-    uint32_t wh[2];
-    if (std::fread(wh, 4, 2, f) != 2) {
-      std::fclose(f);
-      return false;
-    }
-    w = static_cast<int>(wh[0]);
-    h = static_cast<int>(wh[1]);
-    if (w <= 0 || h <= 0 || w > 8192 || h > 8192) {
-      std::fclose(f);
-      return false;
-    }
-    bgra.resize(static_cast<size_t>(w) * h * 4);
-    size_t got = std::fread(bgra.data(), 1, bgra.size(), f);
-    std::fclose(f);
-    return got == bgra.size();
-  }
-
-  void composite(uint8_t* frame, int fw, int fh, int stride, int location,
-                 uint64_t frame_idx) const {
-    if (w == 0) return;
-    int x0 = 0, y0 = 0, margin = 16;
-    switch (location) {
-      case 1: x0 = margin; y0 = margin; break;
-      case 2: x0 = fw - w - margin; y0 = margin; break;
-      case 3: x0 = margin; y0 = fh - h - margin; break;
-      case 4: x0 = fw - w - margin; y0 = fh - h - margin; break;
-      case 5: x0 = (fw - w) / 2; y0 = (fh - h) / 2; break;
-      case 6: {  // bounce animation
-        int sx = std::max(1, fw - w), sy = std::max(1, fh - h);
-        x0 = static_cast<int>((frame_idx * 3) % (2 * sx));
-        y0 = static_cast<int>((frame_idx * 2) % (2 * sy));
-        if (x0 >= sx) x0 = 2 * sx - x0 - 1;
-        if (y0 >= sy) y0 = 2 * sy - y0 - 1;
-        break;
-      }
-      default: return;
-    }
-    for (int y = 0; y < h; ++y) {
-      int fy = y0 + y;
-      if (fy < 0 || fy >= fh) continue;
-      uint8_t* dst = frame + static_cast<size_t>(fy) * stride;
-      const uint8_t* src = bgra.data() + static_cast<size_t>(y) * w * 4;
-      for (int x = 0; x < w; ++x) {
-        int fx = x0 + x;
-        if (fx < 0 || fx >= fw) continue;
-        int a = src[x * 4 + 3];
-        if (a == 0) continue;
-        uint8_t* d = dst + fx * 4;
-        for (int c = 0; c < 3; ++c)
-          d[c] = static_cast<uint8_t>(
-              (src[x * 4 + c] * a + d[c] * (255 - a) + 127) / 255);
-      }
-    }
-  }
-};
-
-}  // namespace
 
 void pack_wire_stripe(const EncodedStripe& s, std::vector<uint8_t>& out) {
   if (s.type == StripeType::kH264 || s.type == StripeType::kHevc) {
@@ -198,11 +127,13 @@ void ScreenCapture::run() {
       std::min(1.0f, std::max(0.25f, settings_.capture_scale));
   const bool frac_scale = fscale < 0.9999f;
   DamageTracker damage;
-  if (frac_scale)
-    damage.reset(std::max(1, int(src->width() * fscale + 0.5f)),
-                 std::max(1, int(src->height() * fscale + 0.5f)));
-  else
-    damage.reset(src->width() / scale_div, src->height() / scale_div);
+  const int damage_w = frac_scale
+                           ? std::max(1, int(src->width() * fscale + 0.5f))
+                           : src->width() / scale_div;
+  const int damage_h = frac_scale
+                           ? std::max(1, int(src->height() * fscale + 0.5f))
+                           : src->height() / scale_div;
+  damage.reset(damage_w, damage_h);
   std::vector<uint8_t> scale_buf;
 
   Watermark watermark;
@@ -214,6 +145,36 @@ void ScreenCapture::run() {
   }
   uint64_t wm_frame = 0;
   uint64_t last_cursor_serial = ~0ULL;
+
+  // Device capture front end (opt-in): overlay, downscale and block diff
+  // run on the GPU and the HIP pipeline gets a device frame. Anything
+  // else takes the host path below.
+  std::unique_ptr<GpuFrontEnd> frontend;
+  frontend_name_.store("host");
+  if (settings_.gpu_frontend) {
+#ifdef HIPFLUX_HAVE_HIP
+    if (std::strncmp(pipeline_name_, "hip", 3) == 0) {
+      try {
+        frontend = make_gpu_frontend(src->width(), src->height(),
+                                     frac_scale ? fscale : 1.0f, scale_div,
+                                     settings_.gpu_id);
+        if (watermark.w > 0)
+          frontend->set_watermark(watermark.bgra.data(), watermark.w,
+                                  watermark.h);
+      } catch (const std::exception& e) {
+        frontend.reset();
+        std::fprintf(stderr, "hipflux: gpu_frontend unavailable (%s)\n",
+                     e.what());
+      }
+    }
+#endif
+    frontend_name_.store(frontend ? "hip" : "host");
+    if (!frontend)
+      std::fprintf(stderr,
+                   "hipflux: gpu_frontend not used with pipeline %s, "
+                   "capture front end stays on the host\n",
+                   pipeline_name_);
+  }
 
   // CBR rate control (video_cbr_mode): VBV-fullness PI controller mapping
   // produced bytes to a per-frame QP within [min_qp, max_qp]. CRF mode
@@ -249,7 +210,43 @@ void ScreenCapture::run() {
     if (settings_.capture_cursor || cursor_cb_)
       have_cursor = src->cursor(cursor);
 
-    if (watermark.w > 0 || (settings_.capture_cursor && have_cursor)) {
+    const double fe_t0 = now_ms();
+    const bool force_all = settings_.video_fullframe;
+    if (frontend) {
+      try {
+        GpuFrontEnd::Overlay ov;
+        if (watermark.w > 0) {
+          ov.wm_location = settings_.watermark_location;
+          ov.wm_frame = wm_frame;
+        }
+        if (settings_.capture_cursor && have_cursor) ov.cursor = &cursor;
+        GpuFrontEnd::Result r = frontend->process(
+            frame, ov, settings_.damage_block_threshold, !force_all);
+        if (watermark.w > 0) ++wm_frame;
+        frame.data = nullptr;   // HIP pipelines read frame.dev
+        frame.dev = r.dev;
+        frame.width = r.width;
+        frame.height = r.height;
+        frame.stride = r.stride;
+        if (!force_all) {
+          if (r.bx != damage.blocks_x() || r.by != damage.blocks_y())
+            damage.reset(r.width, r.height);
+          damage.apply_dirty(r.flags, settings_.damage_block_duration);
+        }
+      } catch (const std::exception& e) {
+        std::fprintf(stderr,
+                     "hipflux: gpu_frontend failed (%s), capture front end "
+                     "back on the host\n",
+                     e.what());
+        frontend.reset();
+        frontend_name_.store("host");
+        damage.reset(damage_w, damage_h);
+      }
+    }
+    const bool host_frontend = !frontend;
+
+    if (host_frontend &&
+        (watermark.w > 0 || (settings_.capture_cursor && have_cursor))) {
       // composite on a scratch copy (the source buffer may persist)
       size_t bytes = static_cast<size_t>(frame.stride) * frame.height;
       wm_scratch.resize(bytes);
@@ -258,27 +255,10 @@ void ScreenCapture::run() {
         watermark.composite(wm_scratch.data(), frame.width, frame.height,
                             frame.stride, settings_.watermark_location,
                             wm_frame++);
-      if (settings_.capture_cursor && have_cursor) {
-        for (int cy = 0; cy < cursor.height; ++cy) {
-          int fy = cursor.y + cy;
-          if (fy < 0 || fy >= frame.height) continue;
-          uint8_t* dst = wm_scratch.data() +
-                         static_cast<size_t>(fy) * frame.stride;
-          for (int cx = 0; cx < cursor.width; ++cx) {
-            int fx = cursor.x + cx;
-            if (fx < 0 || fx >= frame.width) continue;
-            uint32_t p = cursor.argb[static_cast<size_t>(cy) * cursor.width +
-                                     cx];
-            int a = p >> 24;
-            if (a == 0) continue;
-            uint8_t* d = dst + fx * 4;
-            // XFixes pixels are premultiplied ARGB
-            d[0] = clip8u(((p & 0xFF) * 255 + d[0] * (255 - a)) / 255);
-            d[1] = clip8u((((p >> 8) & 0xFF) * 255 + d[1] * (255 - a)) / 255);
-            d[2] = clip8u((((p >> 16) & 0xFF) * 255 + d[2] * (255 - a)) / 255);
-          }
-        }
-      }
+      if (settings_.capture_cursor && have_cursor)
+        composite_cursor(wm_scratch.data(), frame.width, frame.height,
+                         frame.stride, cursor.argb.data(), cursor.width,
+                         cursor.height, cursor.x, cursor.y);
       frame.data = wm_scratch.data();
     }
     if (cursor_cb_ && have_cursor && cursor.serial != last_cursor_serial) {
@@ -290,7 +270,9 @@ void ScreenCapture::run() {
     // capture downscale: fractional bilinear (capture_scale) or exact
     // integer box (capture_scale_div); cursor/watermark were composited
     // at native size above
-    if (frac_scale) {
+    if (!host_frontend) {
+      // scaled on the device
+    } else if (frac_scale) {
       int ow, oh, ostride;
       bilinear_downscale_bgrx(frame.data, frame.stride, frame.width,
                               frame.height, fscale, scale_buf, ow, oh,
@@ -311,10 +293,10 @@ void ScreenCapture::run() {
     }
 
     // damage update (skipped in fullframe mode to save the diff cost)
-    bool force_all = settings_.video_fullframe;
-    if (!force_all)
+    if (host_frontend && !force_all)
       damage.update(frame.data, frame.stride, settings_.damage_block_threshold,
                     settings_.damage_block_duration);
+    last_frontend_ms_.store(now_ms() - fe_t0);
 
     bool idr = idr_requested_.exchange(false);
     double tnow = now_ms();

@@ -120,7 +120,12 @@ class ScreenCapture {
   uint64_t frames_encoded() const { return frames_encoded_.load(); }
   uint64_t stripes_emitted() const { return stripes_emitted_.load(); }
   double last_encode_ms() const { return last_encode_ms_.load(); }
+  // Capture front end of the last frame: overlay + downscale + damage
+  // (host path), or upload + the same on the device (gpu_frontend).
+  double last_frontend_ms() const { return last_frontend_ms_.load(); }
   const char* pipeline_name() const { return pipeline_name_; }
+  // Where the capture front end runs: "hip" (gpu_frontend in use) or "host".
+  const char* frontend_name() const { return frontend_name_.load(); }
 
  private:
   void run();
@@ -141,10 +146,12 @@ class ScreenCapture {
   std::atomic<uint64_t> frames_encoded_{0};
   std::atomic<uint64_t> stripes_emitted_{0};
   std::atomic<double> last_encode_ms_{0.0};
+  std::atomic<double> last_frontend_ms_{0.0};
   std::mutex region_mutex_;
   int region_[4] = {0, 0, 0, 0};
   std::atomic<bool> region_changed_{false};
   const char* pipeline_name_ = "none";
+  std::atomic<const char*> frontend_name_{"host"};
 };
 
 // Pack the wire header in front of an encoded stripe payload

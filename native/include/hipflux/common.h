@@ -37,6 +37,8 @@ struct CaptureSettings {
   bool video_fullframe = false;     // disable damage gating
   bool use_cpu = false;             // force CPU encode path
   int gpu_id = 0;                   // HIP device ordinal (encode_node_index)
+  bool gpu_frontend = false;        // overlay, downscale and damage diff on
+                                    // the GPU (HIP pipelines only; opt-in)
 
   int video_bitrate_kbps = 16000;
   int video_crf = 25;
@@ -94,6 +96,10 @@ struct RawFrame {
   int height = 0;
   int stride = 0;        // bytes per row
   double ts_ms = 0.0;
+  // Set by the device capture front end: the same frame in device memory
+  // (same width/height/stride). The HIP pipelines then copy from here and
+  // leave `data` alone; CPU pipelines never see it.
+  const uint8_t* dev = nullptr;
 };
 
 double now_ms();

@@ -16,8 +16,10 @@
 #include "cpu/opus/celt.h"
 #include "cpu/opus/range_coder.h"
 #include "cpu/jpeg_enc.h"
+#include "cpu/overlay.h"
 #include "cpu/scale.h"
 #include "engine.h"
+#include "frontend_hip.h"
 #include <hip/hip_runtime.h>
 
 #include "rccl_comm.h"
@@ -48,6 +50,7 @@ PYBIND11_MODULE(_native, m) {
       .def_readwrite("video_fullframe", &CaptureSettings::video_fullframe)
       .def_readwrite("use_cpu", &CaptureSettings::use_cpu)
       .def_readwrite("gpu_id", &CaptureSettings::gpu_id)
+      .def_readwrite("gpu_frontend", &CaptureSettings::gpu_frontend)
       .def_readwrite("video_bitrate_kbps", &CaptureSettings::video_bitrate_kbps)
       .def_readwrite("video_crf", &CaptureSettings::video_crf)
       .def_readwrite("video_cbr_mode", &CaptureSettings::video_cbr_mode)
@@ -138,8 +141,12 @@ PYBIND11_MODULE(_native, m) {
       .def_property_readonly("frames_encoded", &ScreenCapture::frames_encoded)
       .def_property_readonly("stripes_emitted", &ScreenCapture::stripes_emitted)
       .def_property_readonly("last_encode_ms", &ScreenCapture::last_encode_ms)
+      .def_property_readonly("last_frontend_ms",
+                             &ScreenCapture::last_frontend_ms)
       .def_property_readonly("pipeline",
-                             [](ScreenCapture& s) { return s.pipeline_name(); });
+                             [](ScreenCapture& s) { return s.pipeline_name(); })
+      .def_property_readonly("frontend",
+                             [](ScreenCapture& s) { return s.frontend_name(); });
 
   // ---- direct encode / test helpers ---------------------------------------
   m.def(
@@ -889,6 +896,305 @@ PYBIND11_MODULE(_native, m) {
       },
       py::arg("bgrx"), py::arg("w"), py::arg("h"), py::arg("scale"),
       "Test hook: exact fixed-point bilinear downscale (engine path).");
+
+  // ---- capture front end: device path + stateful host twin ---------------
+  py::class_<DamageTracker>(m, "_DamageTracker")
+      .def(py::init<>())
+      .def("reset", &DamageTracker::reset, py::arg("width"),
+           py::arg("height"), py::arg("block") = 16)
+      .def(
+          "update",
+          [](DamageTracker& d, py::buffer cur, int stride, int threshold,
+             int duration) {
+            py::buffer_info info = cur.request();
+            d.update(static_cast<const uint8_t*>(info.ptr), stride, threshold,
+                     duration);
+          },
+          py::arg("cur"), py::arg("stride"), py::arg("threshold"),
+          py::arg("duration"))
+      .def(
+          "apply_dirty",
+          [](DamageTracker& d, py::object flags, int duration) {
+            if (flags.is_none()) {
+              d.apply_dirty(nullptr, duration);
+              return;
+            }
+            py::buffer_info info = flags.cast<py::buffer>().request();
+            if (info.size * info.itemsize <
+                static_cast<ssize_t>(d.blocks_x()) * d.blocks_y())
+              throw std::runtime_error("flag map too small");
+            d.apply_dirty(static_cast<const uint8_t*>(info.ptr), duration);
+          },
+          py::arg("flags"), py::arg("duration"),
+          "flags: blocks_x*blocks_y bytes (nonzero = changed), or None = "
+          "everything changed")
+      .def("ages",
+           [](const DamageTracker& d) {
+             return py::array_t<uint16_t>(d.ages().size(), d.ages().data());
+           })
+      .def_property_readonly("blocks_x", &DamageTracker::blocks_x)
+      .def_property_readonly("blocks_y", &DamageTracker::blocks_y)
+      .def("consecutive_still_frames",
+           &DamageTracker::consecutive_still_frames);
+
+  // What both front end hooks share: argument parsing, the cursor's
+  // serial (bumped when the image changes), and the damage tracker, which
+  // restarts when the scaled size or the `damage` argument changes.
+  struct FrontHook {
+    int w, h;
+    float scale;
+    int div;
+    Watermark wm;
+    int wm_location = 0;
+    CursorImage cursor;
+    DamageTracker damage;
+    int dmg_w = 0, dmg_h = 0;
+    bool dmg_on = true;
+
+    FrontHook(int width, int height, float s, int d)
+        : w(width), h(height), scale(std::min(1.0f, std::max(0.25f, s))),
+          div(std::min(4, std::max(1, d))) {}
+
+    RawFrame frame_of(const py::buffer_info& info, int stride, int width,
+                      int height) const {
+      RawFrame f;
+      f.width = width > 0 ? width : w;
+      f.height = height > 0 ? height : h;
+      f.stride = stride > 0 ? stride : f.width * 4;
+      f.data = static_cast<const uint8_t*>(info.ptr);
+      if (f.stride < f.width * 4 || f.stride % 4 ||
+          info.size * info.itemsize <
+              static_cast<ssize_t>(f.stride) * (f.height - 1) + f.width * 4)
+        throw std::runtime_error("buffer too small for the frame geometry");
+      return f;
+    }
+    bool take_cursor(const py::object& c) {
+      if (c.is_none()) return false;
+      py::tuple t = c.cast<py::tuple>();   // (argb, cw, ch, x, y)
+      py::buffer_info bi = t[0].cast<py::buffer>().request();
+      const int cw = t[1].cast<int>(), ch = t[2].cast<int>();
+      if (cw <= 0 || ch <= 0 ||
+          bi.size * bi.itemsize < static_cast<ssize_t>(cw) * ch * 4)
+        throw std::runtime_error("cursor image too small");
+      std::vector<uint32_t> px(static_cast<size_t>(cw) * ch);
+      std::memcpy(px.data(), bi.ptr, px.size() * 4);
+      if (px != cursor.argb || cw != cursor.width || ch != cursor.height) {
+        cursor.argb = std::move(px);
+        ++cursor.serial;
+      }
+      cursor.width = cw;
+      cursor.height = ch;
+      cursor.x = t[3].cast<int>();
+      cursor.y = t[4].cast<int>();
+      return true;
+    }
+    void set_watermark(py::buffer bgra, int ww, int wh, int location) {
+      py::buffer_info info = bgra.request();
+      if (ww <= 0 || wh <= 0 ||
+          info.size * info.itemsize < static_cast<ssize_t>(ww) * wh * 4)
+        throw std::runtime_error("watermark image too small");
+      wm.w = ww;
+      wm.h = wh;
+      const uint8_t* p = static_cast<const uint8_t*>(info.ptr);
+      wm.bgra.assign(p, p + static_cast<size_t>(ww) * wh * 4);
+      wm_location = location;
+    }
+    // true = the tracker was (re)started: the next frame is all dirty
+    bool track(int ow, int oh, bool on) {
+      if (ow == dmg_w && oh == dmg_h && on == dmg_on) return false;
+      damage.reset(ow, oh);
+      dmg_w = ow;
+      dmg_h = oh;
+      dmg_on = on;
+      return true;
+    }
+    py::dict result(const std::vector<uint8_t>& tight, int ow, int oh) const {
+      py::dict d;
+      d["frame"] = py::bytes(reinterpret_cast<const char*>(tight.data()),
+                             tight.size());
+      d["w"] = ow;
+      d["h"] = oh;
+      d["ages"] =
+          py::array_t<uint16_t>(damage.ages().size(), damage.ages().data());
+      d["still_frames"] = damage.consecutive_still_frames();
+      return d;
+    }
+  };
+
+  struct PyGpuFrontEnd : FrontHook {
+    std::unique_ptr<GpuFrontEnd> fe;
+    PyGpuFrontEnd(int width, int height, float s, int d, int gpu_id,
+                  bool pin_source)
+        : FrontHook(width, height, s, d),
+          fe(make_gpu_frontend(width, height, s, d, gpu_id, pin_source)) {}
+  };
+  py::class_<PyGpuFrontEnd>(m, "GpuFrontEnd")
+      .def(py::init<int, int, float, int, int, bool>(), py::arg("width"),
+           py::arg("height"), py::arg("scale") = 1.0f,
+           py::arg("scale_div") = 1, py::arg("gpu_id") = 0,
+           py::arg("pin_source") = false,
+           "Device capture front end. pin_source=True page-locks the frame "
+           "buffers it is given in place: pass only buffers that outlive "
+           "this object.")
+      .def(
+          "set_watermark",
+          [](PyGpuFrontEnd& self, py::buffer bgra, int ww, int wh,
+             int location) {
+            self.set_watermark(bgra, ww, wh, location);
+            self.fe->set_watermark(self.wm.bgra.data(), ww, wh);
+          },
+          py::arg("bgra"), py::arg("w"), py::arg("h"), py::arg("location"))
+      .def("set_timing",
+           [](PyGpuFrontEnd& self, bool on) { self.fe->set_timing(on); })
+      .def("last_stage_ms",
+           [](PyGpuFrontEnd& self) {
+             GpuFrontEnd::StageMs t = self.fe->last_stage_ms();
+             py::dict d;
+             d["h2d"] = t.h2d;
+             d["overlay"] = t.overlay;
+             d["scale"] = t.scale;
+             d["damage"] = t.damage;
+             return d;
+           })
+      .def(
+          "process",
+          [](PyGpuFrontEnd& self, py::buffer bgrx, int stride,
+             py::object cursor, uint64_t frame_idx, int threshold,
+             int duration, bool damage, int width, int height,
+             bool download) {
+            py::buffer_info info = bgrx.request();
+            RawFrame f = self.frame_of(info, stride, width, height);
+            GpuFrontEnd::Overlay ov;
+            if (self.wm.w > 0) {
+              ov.wm_location = self.wm_location;
+              ov.wm_frame = frame_idx;
+            }
+            if (self.take_cursor(cursor)) ov.cursor = &self.cursor;
+            GpuFrontEnd::Result r;
+            std::vector<uint8_t> tight;
+            {
+              py::gil_scoped_release rel;
+              r = self.fe->process(f, ov, threshold, damage);
+              // a restarted tracker (new size, `damage` toggled) takes this
+              // frame as all dirty, like the host twin's update()
+              if (self.track(r.width, r.height, damage)) r.flags = nullptr;
+              if (damage) self.damage.apply_dirty(r.flags, duration);
+              if (download) self.fe->download(tight);
+            }
+            return self.result(tight, r.width, r.height);
+          },
+          py::arg("bgrx"), py::arg("stride") = 0,
+          py::arg("cursor") = py::none(), py::arg("frame_idx") = 0,
+          py::arg("threshold") = 15, py::arg("duration") = 30,
+          py::arg("damage") = true, py::arg("width") = 0,
+          py::arg("height") = 0, py::arg("download") = true,
+          "One frame through upload, overlay, downscale and block diff on "
+          "the GPU -> {frame, w, h, ages, still_frames}. cursor = (argb, cw, "
+          "ch, x, y); width/height 0 = the constructor's; download=False "
+          "leaves frame empty (timing).");
+
+  struct PyCpuFrontEnd : FrontHook {
+    std::vector<uint8_t> scratch, scaled, tight;
+    PyCpuFrontEnd(int width, int height, float s, int d, int, bool)
+        : FrontHook(width, height, s, d) {}
+  };
+  py::class_<PyCpuFrontEnd>(m, "_frontend_cpu")
+      .def(py::init<int, int, float, int, int, bool>(), py::arg("width"),
+           py::arg("height"), py::arg("scale") = 1.0f,
+           py::arg("scale_div") = 1, py::arg("gpu_id") = 0,
+           py::arg("pin_source") = false,
+           "Host twin of GpuFrontEnd: the engine's host code "
+           "(cpu/overlay.h, cpu/scale.h, DamageTracker::update).")
+      .def("set_watermark", &PyCpuFrontEnd::set_watermark, py::arg("bgra"),
+           py::arg("w"), py::arg("h"), py::arg("location"))
+      .def(
+          "process",
+          [](PyCpuFrontEnd& self, py::buffer bgrx, int stride,
+             py::object cursor, uint64_t frame_idx, int threshold,
+             int duration, bool damage, int width, int height,
+             bool download) {
+            py::buffer_info info = bgrx.request();
+            RawFrame f = self.frame_of(info, stride, width, height);
+            const bool have_cursor = self.take_cursor(cursor);
+            int ow = f.width, oh = f.height;
+            {
+              py::gil_scoped_release rel;
+              const uint8_t* data = f.data;
+              if (self.wm.w > 0 || have_cursor) {
+                const size_t bytes =
+                    static_cast<size_t>(f.stride) * (f.height - 1) +
+                    static_cast<size_t>(f.width) * 4;
+                self.scratch.assign(data, data + bytes);
+                if (self.wm.w > 0)
+                  self.wm.composite(self.scratch.data(), f.width, f.height,
+                                    f.stride, self.wm_location, frame_idx);
+                if (have_cursor)
+                  composite_cursor(self.scratch.data(), f.width, f.height,
+                                   f.stride, self.cursor.argb.data(),
+                                   self.cursor.width, self.cursor.height,
+                                   self.cursor.x, self.cursor.y);
+                data = self.scratch.data();
+              }
+              int ostride = f.stride;
+              if (self.scale < 0.9999f) {
+                bilinear_downscale_bgrx(data, f.stride, f.width, f.height,
+                                        self.scale, self.scaled, ow, oh,
+                                        ostride);
+                data = self.scaled.data();
+              } else if (self.div > 1) {
+                box_downscale_bgrx(data, f.stride, f.width, f.height,
+                                   self.div, self.scaled, ow, oh, ostride);
+                data = self.scaled.data();
+              }
+              self.track(ow, oh, damage);
+              if (damage) self.damage.update(data, ostride, threshold, duration);
+              self.tight.clear();
+              if (download) {
+                self.tight.resize(static_cast<size_t>(ow) * oh * 4);
+                for (int y = 0; y < oh; ++y)
+                  std::memcpy(self.tight.data() + static_cast<size_t>(y) * ow * 4,
+                              data + static_cast<size_t>(y) * ostride,
+                              static_cast<size_t>(ow) * 4);
+              }
+            }
+            return self.result(self.tight, ow, oh);
+          },
+          py::arg("bgrx"), py::arg("stride") = 0,
+          py::arg("cursor") = py::none(), py::arg("frame_idx") = 0,
+          py::arg("threshold") = 15, py::arg("duration") = 30,
+          py::arg("damage") = true, py::arg("width") = 0,
+          py::arg("height") = 0, py::arg("download") = true);
+
+  m.def(
+      "_d2d_copy_ms",
+      [](size_t bytes, int iters) {
+        // device-to-device hipMemcpyAsync of `bytes`: the yardstick the
+        // front end's streaming kernels are reported against
+        void *a = nullptr, *b = nullptr;
+        hipEvent_t e0, e1;
+        if (hipMalloc(&a, bytes) != hipSuccess ||
+            hipMalloc(&b, bytes) != hipSuccess) {
+          (void)hipFree(a);
+          throw std::runtime_error("hipMalloc failed");
+        }
+        (void)hipEventCreate(&e0);
+        (void)hipEventCreate(&e1);
+        (void)hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, nullptr);
+        (void)hipEventRecord(e0, nullptr);
+        for (int i = 0; i < iters; ++i)
+          (void)hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, nullptr);
+        (void)hipEventRecord(e1, nullptr);
+        (void)hipEventSynchronize(e1);
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        (void)hipFree(a);
+        (void)hipFree(b);
+        return ms / std::max(1, iters);
+      },
+      py::arg("bytes"), py::arg("iters") = 20,
+      "Mean ms of one device-to-device copy of `bytes` (tools).");
 
   m.def(
       "screenshot",

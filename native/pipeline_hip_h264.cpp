@@ -77,9 +77,14 @@ class HipH264Pipeline : public EncodePipeline {
     // serialized on the compute stream); the compute stream's CSC waits
     // on the copy via event
     const size_t frame_bytes = static_cast<size_t>(frame.stride) * frame.height;
-    HIP_CHECK(hipMemcpyAsync(d_frame_[par],
-                             uploader_.source(frame.data, frame_bytes),
-                             frame_bytes, hipMemcpyHostToDevice, up_stream_));
+    if (frame.dev)   // front-end frame: already complete on the device
+      HIP_CHECK(hipMemcpyAsync(d_frame_[par], frame.dev, frame_bytes,
+                               hipMemcpyDeviceToDevice, up_stream_));
+    else
+      HIP_CHECK(hipMemcpyAsync(d_frame_[par],
+                               uploader_.source(frame.data, frame_bytes),
+                               frame_bytes, hipMemcpyHostToDevice,
+                               up_stream_));
     // the caller may reuse its frame buffer once this event completes
     HIP_CHECK(hipEventRecord(ev_h2d_[par], up_stream_));
     // the whole produce chain (CSC -> ME -> rows) rides rows_stream_ so

@@ -58,10 +58,14 @@ class HipHevcPipeline : public EncodePipeline {
     // frame N+1's upload/CSC/rows run on rows_stream_, concurrent with
     // frame N's CABAC on stream_ (levels/meta are parity
     // double-buffered; the recon planes have no cross-frame reader)
-    HIP_CHECK(hipMemcpyAsync(d_frame_[par],
-                             uploader_.source(frame.data, frame_bytes),
-                             frame_bytes, hipMemcpyHostToDevice,
-                             rows_stream_));
+    if (frame.dev)   // front-end frame: already complete on the device
+      HIP_CHECK(hipMemcpyAsync(d_frame_[par], frame.dev, frame_bytes,
+                               hipMemcpyDeviceToDevice, rows_stream_));
+    else
+      HIP_CHECK(hipMemcpyAsync(d_frame_[par],
+                               uploader_.source(frame.data, frame_bytes),
+                               frame_bytes, hipMemcpyHostToDevice,
+                               rows_stream_));
     HIP_CHECK(hipEventRecord(ev_h2d_[par], rows_stream_));
     launch_bgrx_to_planes(d_frame_[par], w_, h_, frame.stride / 4, d_srcY_,
                           d_srcCb_, d_srcCr_, ypitch_, cpitch_, false,

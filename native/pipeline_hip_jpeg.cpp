@@ -60,10 +60,14 @@ class HipJpegPipeline : public EncodePipeline {
     // produce chain (upload, CSC, DCT) on its own stream so it overlaps
     // the previous frame's entropy kernel + readback on stream_
     const size_t frame_bytes = static_cast<size_t>(frame.stride) * frame.height;
-    HIP_CHECK(hipMemcpyAsync(d_frame2_[par],
-                             uploader_.source(frame.data, frame_bytes),
-                             frame_bytes, hipMemcpyHostToDevice,
-                             prod_stream_));
+    if (frame.dev)   // front-end frame: already complete on the device
+      HIP_CHECK(hipMemcpyAsync(d_frame2_[par], frame.dev, frame_bytes,
+                               hipMemcpyDeviceToDevice, prod_stream_));
+    else
+      HIP_CHECK(hipMemcpyAsync(d_frame2_[par],
+                               uploader_.source(frame.data, frame_bytes),
+                               frame_bytes, hipMemcpyHostToDevice,
+                               prod_stream_));
 
     const int stride_px = frame.stride / 4;
     const int stripe_h = std::max(16, settings_.stripe_height & ~15);
