@@ -39,6 +39,7 @@ struct StripeEncoder::Impl {
   int cw, ch;          // coded (16-aligned)
   int ctb_w, ctb_h;    // CTUs per row / rows
   int slices_per_row;
+  bool fullcolor;      // 4:4:4: chroma planes are luma-sized
   int addr_bits;
   std::vector<uint8_t> ry, rcb, rcr;        // recon planes (coded dims)
   std::vector<uint8_t> sy, scb, scr;        // padded source planes
@@ -46,24 +47,25 @@ struct StripeEncoder::Impl {
   std::vector<uint8_t> ps_cache;            // VPS/SPS/PPS bytes
   int ypitch, cpitch;
 
-  Impl(int width, int height, int spr)
+  Impl(int width, int height, int spr, bool fc)
       : w(width), h(height), cw((width + 15) & ~15), ch((height + 15) & ~15),
         ctb_w(cw / 16), ctb_h(ch / 16),
-        slices_per_row(std::max(1, std::min(spr, cw / 16))) {
+        slices_per_row(std::max(1, std::min(spr, cw / 16))), fullcolor(fc) {
     int n_ctb = ctb_w * ctb_h;
     addr_bits = 1;
     while ((1 << addr_bits) < n_ctb) ++addr_bits;
     ypitch = cw;
-    cpitch = cw / 2;
+    cpitch = fullcolor ? cw : cw / 2;
+    const int crows = fullcolor ? ch : ch / 2;
     ry.resize(static_cast<size_t>(ypitch) * ch);
-    rcb.resize(static_cast<size_t>(cpitch) * ch / 2);
-    rcr.resize(static_cast<size_t>(cpitch) * ch / 2);
+    rcb.resize(static_cast<size_t>(cpitch) * crows);
+    rcr.resize(static_cast<size_t>(cpitch) * crows);
     sy = ry;
     scb = rcb;
     scr = rcr;
     luma_mode.resize(n_ctb);
-    write_vps_nal(ps_cache, level_idc_for(cw, ch));
-    write_sps_nal(ps_cache, cw, ch, w, h);
+    write_vps_nal(ps_cache, level_idc_for(cw, ch), fullcolor);
+    write_sps_nal(ps_cache, cw, ch, w, h, fullcolor);
     write_pps_nal(ps_cache);
   }
 
@@ -78,6 +80,12 @@ struct StripeEncoder::Impl {
         sy[static_cast<size_t>(r) * ypitch + x] = sy[r * ypitch + w - 1];
     }
     int cwh = cw / 2, chh = ch / 2, wh = (w + 1) / 2, hh = (h + 1) / 2;
+    if (fullcolor) {
+      cwh = cw;
+      chh = ch;
+      wh = w;
+      hh = h;
+    }
     for (int r = 0; r < chh; ++r) {
       int sr = std::min(r, hh - 1);
       std::memcpy(&scb[static_cast<size_t>(r) * cpitch],
@@ -151,6 +159,12 @@ struct StripeEncoder::Impl {
                     &pred[best][yy * 16], 16);
     }
 
+    if (fullcolor) {
+      encode_ctu_chroma444(cab, bank, x0, y0, av, qp, mode, left_avail,
+                           left_mode, yb);
+      return;
+    }
+
     // --- chroma (DM mode), 8x8 TBs
     const int qpc = chroma_qp(qp);
     TbData<8> cbb, crb;
@@ -190,10 +204,60 @@ struct StripeEncoder::Impl {
     code_ctu_syntax(cab, bank, mode, left_avail ? left_mode : -1, yb.cbf,
                     cbb.cbf, crb.cbf, yb.level, cbb.level, crb.level);
   }
+
+  // 4:4:4 chroma (DM mode): Cb and Cr are 16x16 TBs coded like luma with
+  // cIdx 1/2, then the CTU's bins are emitted.
+  void encode_ctu_chroma444(CabacEncoder& cab, ContextBank& bank, int x0,
+                            int y0, const Avail& av, int qp, int mode,
+                            bool left_avail, uint8_t left_mode,
+                            const TbData<16>& yb) {
+    // ChromaArrayType != 1: QpC = Min(qPi, 51), not the Table 8-10 map
+    const int qpc = chroma_qp_444(qp);
+    TbData<16> tb[2];
+    for (int pl = 0; pl < 2; ++pl) {
+      uint8_t* rp = pl ? rcr.data() : rcb.data();
+      const uint8_t* sp = pl ? scr.data() : scb.data();
+      uint8_t cref[65], creff[65], cpred[256];
+      build_refs<16>(rp, cpitch, x0, y0, av, cref);
+      // §8.4.4.2.3: neighbour smoothing applies when cIdx == 0 or
+      // ChromaArrayType == 3. At nTbS 16 the threshold is 1: Planar
+      // (distance 10) filters, DC/H/V (exempt / distance 0) do not.
+      // The DC edge filter and H/V boundary adjust stay cIdx == 0 only
+      // (predict<> with cidx 1).
+      const bool filt = mode == kPlanar;
+      if (filt) filter_refs<16>(cref, creff);
+      predict<16>(mode, filt ? creff : cref, 1, cpred);
+      int16_t cres[256], ccoef[256];
+      for (int yy = 0; yy < 16; ++yy)
+        for (int xx = 0; xx < 16; ++xx)
+          cres[yy * 16 + xx] = static_cast<int16_t>(
+              sp[static_cast<size_t>(y0 + yy) * cpitch + x0 + xx] -
+              cpred[yy * 16 + xx]);
+      fwd_transform<16>(cres, 16, ccoef);
+      tb[pl].cbf = quantize<16>(ccoef, qpc, tb[pl].level) != 0;
+      if (tb[pl].cbf) {
+        int16_t deq[256], rres[256];
+        dequantize<16>(tb[pl].level, qpc, deq);
+        inv_transform<16>(deq, rres, 16);
+        for (int yy = 0; yy < 16; ++yy)
+          for (int xx = 0; xx < 16; ++xx)
+            rp[static_cast<size_t>(y0 + yy) * cpitch + x0 + xx] =
+                clip8(cpred[yy * 16 + xx] + rres[yy * 16 + xx]);
+      } else {
+        for (int yy = 0; yy < 16; ++yy)
+          std::memcpy(&rp[static_cast<size_t>(y0 + yy) * cpitch + x0],
+                      &cpred[yy * 16], 16);
+      }
+    }
+    code_ctu_syntax(cab, bank, mode, left_avail ? left_mode : -1, yb.cbf,
+                    tb[0].cbf, tb[1].cbf, yb.level, tb[0].level, tb[1].level,
+                    true);
+  }
 };
 
-StripeEncoder::StripeEncoder(int width, int height, int slices_per_row)
-    : impl_(new Impl(width, height, slices_per_row)),
+StripeEncoder::StripeEncoder(int width, int height, int slices_per_row,
+                             bool fullcolor)
+    : impl_(new Impl(width, height, slices_per_row, fullcolor)),
       width_(width),
       height_(height) {}
 

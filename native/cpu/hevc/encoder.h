@@ -3,9 +3,10 @@
 // Design (GPU-parallel-first, mirroring the H.264 engine's proven shape —
 // see native/cpu/h264/encoder.h; no reference-project counterpart exists,
 // pixelflux has no HEVC):
-//  * Main profile, all-intra (every frame IDR), CABAC, 4:2:0, bit depth 8.
-//  * CTU = CU = PU = 16x16, one 16x16 luma TB + two 8x8 chroma TBs, no
-//    residual quadtree. This keeps the flat per-16px-row geometry the
+//  * Main profile, all-intra (every frame IDR), CABAC, 4:2:0, bit depth 8;
+//    or with `fullcolor` Main 4:4:4 (chroma_format_idc 3).
+//  * CTU = CU = PU = 16x16, one 16x16 luma TB + two 8x8 chroma TBs (two
+//    16x16 chroma TBs in 4:4:4), no residual quadtree. This keeps the flat per-16px-row geometry the
 //    stripe wire format and the HIP row-wavefront kernels are built
 //    around, and needs only the well-conditioned T16/T8 transforms.
 //  * ONE SLICE SEGMENT PER CTU ROW (optionally split into segments):
@@ -57,13 +58,17 @@ class StripeEncoder {
  public:
   // width/height: visible stripe dims (coded dims round up to 16 with a
   // conformance-window crop). slices_per_row splits each CTU row into
-  // independent slice segments for entropy parallelism.
-  StripeEncoder(int width, int height, int slices_per_row = 1);
+  // independent slice segments for entropy parallelism. fullcolor codes
+  // 4:4:4 (Main 4:4:4 profile, chroma TBs 16x16) instead of 4:2:0.
+  StripeEncoder(int width, int height, int slices_per_row = 1,
+                bool fullcolor = false);
   ~StripeEncoder();
 
   // Encode one frame from planar YUV420 (pitch in bytes, planes at least
   // coded-size with any padding content; qp in [0,51]). Appends Annex-B
-  // (VPS+SPS+PPS+IDR slices) to `out`.
+  // (VPS+SPS+PPS+IDR slices) to `out`. A fullcolor encoder takes
+  // full-resolution Cb/Cr (I444) with cpitch, and its recon chroma planes
+  // are coded-size with recon_cpitch() == recon_ypitch().
   void encode_frame(const uint8_t* y, int ypitch, const uint8_t* cb,
                     const uint8_t* cr, int cpitch, int qp,
                     std::vector<uint8_t>& out, EncodeStats* stats = nullptr);

@@ -15,7 +15,8 @@ namespace hipflux {
 namespace hevc {
 
 // ---- residual_coding (§7.3.8.11) for one TB ------------------------------
-// N = 16 (luma) or 8 (chroma). Levels indexed [y*N + x].
+// N = 16 (luma, and chroma in 4:4:4) or 8 (4:2:0 chroma). Levels indexed
+// [y*N + x].
 template <int N>
 inline void code_residual(CabacEncoder& cab, ContextBank& bank,
                    const int16_t* level, int cidx) {
@@ -231,7 +232,8 @@ inline void code_residual(CabacEncoder& cab, ContextBank& bank,
 inline void code_ctu_syntax(CabacEncoder& cab, ContextBank& bank, int mode,
                             int left_mode, bool cbf_y, bool cbf_cb,
                             bool cbf_cr, const int16_t* ylv,
-                            const int16_t* cblv, const int16_t* crlv) {
+                            const int16_t* cblv, const int16_t* crlv,
+                            bool fullcolor = false) {
   cab.encode_bin(bank.ctx[kCtxSplitCu + 0], 0);  // split_cu_flag
   // MPM derivation (§8.4.2): above PU is outside the CTU row -> DC.
   int cand_a = left_mode >= 0 ? left_mode : kDc;
@@ -278,8 +280,19 @@ inline void code_ctu_syntax(CabacEncoder& cab, ContextBank& bank, int mode,
   cab.encode_bin(bank.ctx[kCtxCbfChroma + 0], cbf_cr ? 1 : 0);
   cab.encode_bin(bank.ctx[kCtxCbfLuma + 1], cbf_y ? 1 : 0);
   if (cbf_y) code_residual<16>(cab, bank, ylv, 0);
-  if (cbf_cb) code_residual<8>(cab, bank, cblv, 1);
-  if (cbf_cr) code_residual<8>(cab, bank, crlv, 2);
+  if (fullcolor) {
+    // ChromaArrayType 3: the chroma TBs are 16x16 like luma (§7.3.8.10,
+    // log2TrafoSizeC = log2TrafoSize). residual_coding picks its chroma
+    // contexts from cIdx > 0 alone: last-pos ctxOffset 15 with
+    // ctxShift = log2TrafoSize - 2, sig_coeff +12 (+27 bank offset),
+    // coded_sub_block +2, greater1 +16, greater2 +4. The scan stays
+    // diagonal (mode-dependent scans stop at log2TrafoSize 3).
+    if (cbf_cb) code_residual<16>(cab, bank, cblv, 1);
+    if (cbf_cr) code_residual<16>(cab, bank, crlv, 2);
+  } else {
+    if (cbf_cb) code_residual<8>(cab, bank, cblv, 1);
+    if (cbf_cr) code_residual<8>(cab, bank, crlv, 2);
+  }
 }
 
 }  // namespace hevc

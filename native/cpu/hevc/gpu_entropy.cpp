@@ -24,19 +24,21 @@ void assemble_hevc_slice_nal(const uint8_t* cabac_bytes, int n_bytes,
 void encode_hevc_job_nal(const int16_t* levels, const int* meta, int ctbw,
                          int ctu_row, int ctu_x0, int seg_w, int qp,
                          bool first_slice, int slice_addr, int addr_bits,
-                         std::vector<uint8_t>& out) {
+                         std::vector<uint8_t>& out, bool fullcolor) {
   std::vector<uint8_t> cabac_bytes;
   CabacEncoder cab(cabac_bytes);
   ContextBank bank;
   bank.init(qp);
   int left_mode = -1;
+  const int stride = fullcolor ? hevcgpu::kHevcLevelsPerCtu444
+                               : hevcgpu::kHevcLevelsPerCtu;
   for (int ci = 0; ci < seg_w; ++ci) {
     const size_t mb = static_cast<size_t>(ctu_row) * ctbw + ctu_x0 + ci;
     const int mode = meta[mb * hevcgpu::kHevcMetaPerCtu + 0];
     const int cbf = meta[mb * hevcgpu::kHevcMetaPerCtu + 1];
-    const int16_t* lv = levels + mb * hevcgpu::kHevcLevelsPerCtu;
+    const int16_t* lv = levels + mb * stride;
     code_ctu_syntax(cab, bank, mode, left_mode, cbf & 1, cbf & 2, cbf & 4,
-                    lv, lv + 256, lv + 320);
+                    lv, lv + 256, lv + (fullcolor ? 512 : 320), fullcolor);
     left_mode = mode;
     cab.encode_terminate(ci == seg_w - 1 ? 1 : 0);
   }
@@ -48,9 +50,10 @@ void encode_hevc_job_nal(const int16_t* levels, const int* meta, int ctbw,
 }
 
 void write_hevc_stripe_headers(int coded_w, int coded_h, int vis_w,
-                               int vis_h, std::vector<uint8_t>& out) {
-  write_vps_nal(out, level_idc_for(coded_w, coded_h));
-  write_sps_nal(out, coded_w, coded_h, vis_w, vis_h);
+                               int vis_h, std::vector<uint8_t>& out,
+                               bool fullcolor) {
+  write_vps_nal(out, level_idc_for(coded_w, coded_h), fullcolor);
+  write_sps_nal(out, coded_w, coded_h, vis_w, vis_h, fullcolor);
   write_pps_nal(out);
 }
 

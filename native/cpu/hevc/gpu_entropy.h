@@ -18,14 +18,17 @@ void assemble_hevc_slice_nal(const uint8_t* cabac_bytes, int n_bytes,
 // CPU-entropy fallback: encode one slice segment's CABAC from GPU
 // levels/meta (frame-wide layout) and wrap it. Byte-identical to the GPU
 // CABAC kernel; used to isolate rows-kernel vs entropy-kernel bugs.
+// fullcolor selects the 4:4:4 level layout (768 levels per CTU).
 void encode_hevc_job_nal(const int16_t* levels, const int* meta, int ctbw,
                          int ctu_row, int ctu_x0, int seg_w, int qp,
                          bool first_slice, int slice_addr, int addr_bits,
-                         std::vector<uint8_t>& out);
+                         std::vector<uint8_t>& out, bool fullcolor = false);
 
-// Per-stripe parameter sets (VPS+SPS+PPS for a w x h stripe picture).
+// Per-stripe parameter sets (VPS+SPS+PPS for a w x h stripe picture);
+// fullcolor writes the Main 4:4:4 forms.
 void write_hevc_stripe_headers(int coded_w, int coded_h, int vis_w,
-                               int vis_h, std::vector<uint8_t>& out);
+                               int vis_h, std::vector<uint8_t>& out,
+                               bool fullcolor = false);
 
 }  // namespace hevc
 }  // namespace hipflux

@@ -39,22 +39,46 @@ inline int level_idc_for(int w, int h) {
   return 183;                      // 6.1 (8K60)
 }
 
-// profile_tier_level for Main profile (§7.3.3).
-inline void write_ptl(BitWriter& b, int level_idc) {
+// profile_tier_level (§7.3.3): Main, or with fullcolor the format range
+// extensions profile Main 4:4:4 (H.265 v2, §A.3.7).
+inline void write_ptl(BitWriter& b, int level_idc, bool fullcolor = false) {
   b.u(0, 2);            // general_profile_space
   b.u(0, 1);            // general_tier_flag
-  b.u(1, 5);            // general_profile_idc: Main
-  b.u(0x60000000, 32);  // compatibility flags: bits 1 (Main) + 2 (Main 10)
+  if (fullcolor) {
+    b.u(4, 5);            // general_profile_idc: format range extensions
+    b.u(0x08000000, 32);  // compatibility flags: bit 4 only
+  } else {
+    b.u(1, 5);            // general_profile_idc: Main
+    b.u(0x60000000, 32);  // compatibility flags: bits 1 (Main) + 2 (Main 10)
+  }
   b.u(1, 1);            // general_progressive_source_flag
   b.u(0, 1);            // general_interlaced_source_flag
   b.u(1, 1);            // general_non_packed_constraint_flag
   b.u(1, 1);            // general_frame_only_constraint_flag
-  b.u(0, 22);           // general_reserved_zero_44bits
-  b.u(0, 22);
+  if (fullcolor) {
+    // For profile_idc 4 the first 9 of Main's 43 reserved-zero bits are
+    // the RExt constraint flags; Main 4:4:4 is the Table A.2 row
+    b.u(1, 1);          // general_max_12bit_constraint_flag
+    b.u(1, 1);          // general_max_10bit_constraint_flag
+    b.u(1, 1);          // general_max_8bit_constraint_flag
+    b.u(0, 1);          // general_max_422chroma_constraint_flag
+    b.u(0, 1);          // general_max_420chroma_constraint_flag
+    b.u(0, 1);          // general_max_monochrome_constraint_flag
+    b.u(0, 1);          // general_intra_constraint_flag
+    b.u(0, 1);          // general_one_picture_only_constraint_flag
+    b.u(1, 1);          // general_lower_bit_rate_constraint_flag
+    b.u(0, 17);         // general_reserved_zero_34bits
+    b.u(0, 17);
+    b.u(0, 1);          // general_inbld_flag / reserved_zero_bit
+  } else {
+    b.u(0, 22);         // general_reserved_zero_43bits + reserved_zero_bit
+    b.u(0, 22);
+  }
   b.u(level_idc, 8);
 }
 
-inline void write_vps_nal(std::vector<uint8_t>& out, int level_idc) {
+inline void write_vps_nal(std::vector<uint8_t>& out, int level_idc,
+                          bool fullcolor = false) {
   BitWriter b;
   b.u(0, 4);   // vps_video_parameter_set_id
   b.u(1, 1);   // vps_base_layer_internal_flag
@@ -63,7 +87,7 @@ inline void write_vps_nal(std::vector<uint8_t>& out, int level_idc) {
   b.u(0, 3);   // vps_max_sub_layers_minus1
   b.u(1, 1);   // vps_temporal_id_nesting_flag
   b.u(0xFFFF, 16);  // vps_reserved_0xffff_16bits
-  write_ptl(b, level_idc);
+  write_ptl(b, level_idc, fullcolor);
   b.u(1, 1);   // vps_sub_layer_ordering_info_present (code layer 0)
   b.ue(0);     // vps_max_dec_pic_buffering_minus1
   b.ue(0);     // vps_max_num_reorder_pics
@@ -77,21 +101,30 @@ inline void write_vps_nal(std::vector<uint8_t>& out, int level_idc) {
 }
 
 // Coded dims are 16-aligned; visible dims signal via conformance window.
+// fullcolor: chroma_format_idc 3 with joint planes (ChromaArrayType 3);
+// the window offsets are then in units of SubWidthC = SubHeightC = 1, so
+// odd visible sizes crop exactly. No SPS range extension is needed.
 inline void write_sps_nal(std::vector<uint8_t>& out, int coded_w, int coded_h,
-                          int width, int height) {
+                          int width, int height, bool fullcolor = false) {
   BitWriter b;
   b.u(0, 4);   // sps_video_parameter_set_id
   b.u(0, 3);   // sps_max_sub_layers_minus1
   b.u(1, 1);   // sps_temporal_id_nesting_flag
-  write_ptl(b, level_idc_for(coded_w, coded_h));
+  write_ptl(b, level_idc_for(coded_w, coded_h), fullcolor);
   b.ue(0);     // sps_seq_parameter_set_id
-  b.ue(1);     // chroma_format_idc: 4:2:0
+  if (fullcolor) {
+    b.ue(3);     // chroma_format_idc: 4:4:4
+    b.u(0, 1);   // separate_colour_plane_flag
+  } else {
+    b.ue(1);     // chroma_format_idc: 4:2:0
+  }
   b.ue(coded_w);
   b.ue(coded_h);
-  int crop_r = (coded_w - width) / 2, crop_b = (coded_h - height) / 2;
+  const int sub = fullcolor ? 1 : 2;   // SubWidthC == SubHeightC
+  int crop_r = (coded_w - width) / sub, crop_b = (coded_h - height) / sub;
   if (crop_r || crop_b) {
     b.u(1, 1);         // conformance_window_flag
-    b.ue(0);           // left (units of 2 luma samples)
+    b.ue(0);           // left (units of SubWidthC luma samples)
     b.ue(crop_r);
     b.ue(0);
     b.ue(crop_b);

@@ -119,6 +119,15 @@ inline int chroma_qp(int qp_y) {
   return map[qp_y - 30];
 }
 
+// Chroma QP for ChromaArrayType != 1 (§8.6.1, eq. 8-259 family): the
+// Table 8-10 mapping is 4:2:0-only; for 4:4:4 QpC = Min(qPi, 51), which
+// with zero pps/slice chroma offsets is the luma QP itself.
+inline int chroma_qp_444(int qp_y) { return qp_y < 51 ? qp_y : 51; }
+
+inline int chroma_qp_for(int qp_y, bool fullcolor) {
+  return fullcolor ? chroma_qp_444(qp_y) : chroma_qp(qp_y);
+}
+
 // ---- Transform matrices (§8.6.4.2; integer DCT-II approximations) --------
 // T8 full matrix; T16 full matrix. Row k of the inverse transform uses
 // column k of these (matrices are listed in forward orientation:

@@ -4,6 +4,11 @@
 //     +0    .. 255 : luma 16x16 quantized levels, raster [y*16+x]
 //     +256  .. 319 : Cb 8x8 levels
 //     +320  .. 383 : Cr 8x8 levels
+// 4:4:4 (fullcolor) CTUs hold three full blocks instead:
+//   levels[(ctu_row * ctbw + ctu_x) * kHevcLevelsPerCtu444]
+//     +0    .. 255 : luma 16x16
+//     +256  .. 511 : Cb 16x16
+//     +512  .. 767 : Cr 16x16
 //   meta[(ctu_row * ctbw + ctu_x) * kHevcMetaPerCtu]
 //     +0 : chosen intra mode (0 planar / 1 dc / 10 hor / 26 ver)
 //     +1 : cbf mask (bit0 luma, bit1 cb, bit2 cr)
@@ -15,6 +20,7 @@ namespace hipflux {
 namespace hevcgpu {
 
 constexpr int kHevcLevelsPerCtu = 384;
+constexpr int kHevcLevelsPerCtu444 = 768;
 constexpr int kHevcMetaPerCtu = 2;
 
 // One slice-segment job (one CABAC stream; one row-kernel workgroup).
@@ -23,7 +29,8 @@ struct HevcJob {
   int ctu_x0;       // first CTU x of this segment
   int seg_w;        // CTUs in this segment
   int qp;           // luma QP
-  int qpc;          // chroma QP (host-computed Table 8-10 mapping)
+  int qpc;          // chroma QP (host-computed: Table 8-10 mapping for
+                    // 4:2:0, Min(qp, 51) for 4:4:4)
   int first_slice;  // 1 = first slice segment of its stripe picture
   int slice_addr;   // CTU address within the stripe picture
   int addr_bits;    // bits of slice_segment_address in this stripe

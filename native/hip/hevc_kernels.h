@@ -20,13 +20,23 @@ void launch_hevc_rows(const uint8_t* d_srcY, const uint8_t* d_srcCb,
                       const HevcJob* d_jobs, int16_t* d_levels, int* d_meta,
                       hipStream_t stream);
 
+// 4:4:4 form of the above: one 768-thread workgroup per job, the three
+// planes (all pitch `pitch`, full-size chroma) side by side after the luma
+// mode decision. Levels use the kHevcLevelsPerCtu444 layout.
+void launch_hevc_rows444(const uint8_t* d_srcY, const uint8_t* d_srcCb,
+                         const uint8_t* d_srcCr, int pitch, int w, int h,
+                         uint8_t* d_curY, uint8_t* d_curCb, uint8_t* d_curCr,
+                         int ctbw, int n_jobs, const HevcJob* d_jobs,
+                         int16_t* d_levels, int* d_meta, hipStream_t stream);
+
 // Per-job CABAC: one lane per job encodes the slice segment's bins from
 // levels/meta. Output bytes at d_out[job * out_stride_bytes]; d_counts
-// packs {n_bytes, tail_bits, tail_nbits} as 3 ints per job.
+// packs {n_bytes, tail_bits, tail_nbits} as 3 ints per job. fullcolor
+// reads the 4:4:4 level layout and codes 16x16 chroma residuals.
 void launch_hevc_cabac(const int16_t* d_levels, const int* d_meta, int ctbw,
                        int n_jobs, const HevcJob* d_jobs, uint8_t* d_out,
                        int out_stride_bytes, int* d_counts,
-                       hipStream_t stream);
+                       hipStream_t stream, bool fullcolor = false);
 
 }  // namespace hevcgpu
 }  // namespace hipflux

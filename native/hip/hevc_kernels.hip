@@ -8,6 +8,8 @@
 //    pixels of a CTU are processed by one thread each; the 16x16
 //    transforms run as two 16-MAC-per-thread stages through LDS; chroma
 //    8x8 planes run on threads 0..63 / 64..127 concurrently.
+//  * k_hevc_rows444: the 4:4:4 (fullcolor) form; three 16x16 planes side
+//    by side on a 768-thread workgroup (see its own header).
 //  * k_hevc_cabac: CABAC is bin-serial per slice, so one LANE encodes one
 //    slice segment; parallelism comes from the many independent segments
 //    (4K: 135 rows x slices/row). The bin semantics transliterate
@@ -384,6 +386,198 @@ void launch_hevc_rows(const uint8_t* d_srcY, const uint8_t* d_srcCb,
                      d_curCb, d_curCr, ctbw, d_jobs, d_levels, d_meta);
 }
 
+// ---- rows kernel, 4:4:4 --------------------------------------------------
+// ChromaArrayType 3: Cb and Cr are full 16x16 blocks coded exactly like
+// luma apart from the QP (qpc), the luma-only edge filters and the shared
+// (DM) mode. After the luma mode decision the three planes are independent,
+// so they run side by side on a 768-thread workgroup (12 waves):
+// plane = tid >> 8 is wave-uniform, lt = tid & 255 is the pixel. The
+// per-CTU left-to-right chain is this kernel's latency, which is why the
+// planes are not looped over one 256-thread group.
+struct RowsShared444 {
+  int lcol[3][16];    // left CTU's recon right column, per plane
+  int lf[3][16];      // [1 2 1]-filtered left column (planar, all planes)
+  short res[3][256];  // residual / inverse stage buffer
+  int tmp[3][256];    // transform intermediate
+  short coef[3][256]; // quantized levels
+  int sad[4];
+  int best;           // chosen mode index 0..3
+  int cbf;            // bit0 luma, bit1 cb, bit2 cr
+};
+
+// One pixel of the prediction for `mode` from the closed-form references
+// (file header). l0/lty/l15: raw left column samples (128 with no left
+// neighbour), lf: filtered left[ty], dc: DC value of the block.
+// §8.4.4.2.3 smooths the references when cIdx == 0 || ChromaArrayType == 3,
+// so Planar reads the filtered column for every plane here; the DC edge
+// filter (§8.4.4.2.5) and the H/V boundary adjust (§8.4.4.2.6) remain
+// cIdx == 0 only.
+__device__ __forceinline__ int pred444(int mode, bool luma, int tx, int ty,
+                                       int l0, int lty, int l15, int lf,
+                                       int dc) {
+  if (mode == 1) {
+    if (!luma) return dc;
+    if (tx == 0 && ty == 0) return (lty + 2 * dc + l0 + 2) >> 2;
+    if (ty == 0) return (l0 + 3 * dc + 2) >> 2;
+    if (tx == 0) return (lty + 3 * dc + 2) >> 2;
+    return dc;
+  }
+  if (mode == 10) return lty;   // first-row adjust is identity (top == corner)
+  if (mode == 26)
+    return (luma && tx == 0) ? clip8d(l0 + ((lty - l0) >> 1)) : l0;
+  return ((15 - tx) * lf + (tx + 1) * l0 + (15 - ty) * l0 + (ty + 1) * l15 +
+          16) >> 5;
+}
+
+__global__ __launch_bounds__(768) void k_hevc_rows444(
+    const uint8_t* __restrict__ srcY, const uint8_t* __restrict__ srcCb,
+    const uint8_t* __restrict__ srcCr, int pitch, int w, int h,
+    uint8_t* __restrict__ curY, uint8_t* __restrict__ curCb,
+    uint8_t* __restrict__ curCr, int ctbw, const HevcJob* __restrict__ jobs,
+    int16_t* __restrict__ levels, int* __restrict__ meta) {
+  __shared__ RowsShared444 sh;
+  const HevcJob job = jobs[blockIdx.x];
+  const int tid = threadIdx.x;
+  const int pl = tid >> 8;            // 0 Y, 1 Cb, 2 Cr (wave-uniform)
+  const int lt = tid & 255;
+  const int tx = lt & 15, ty = lt >> 4;
+  const bool luma = pl == 0;
+  // ChromaArrayType != 1: the host sets qpc = Min(qp, 51)
+  const int q = luma ? job.qp : job.qpc;
+  const int y0 = job.ctu_row * 16;
+  const uint8_t* src = pl == 0 ? srcY : pl == 1 ? srcCb : srcCr;
+  uint8_t* cur = pl == 0 ? curY : pl == 1 ? curCb : curCr;
+
+  for (int ci = 0; ci < job.seg_w; ++ci) {
+    const int cx = job.ctu_x0 + ci;
+    const int x0 = cx * 16;
+    const bool has_left = ci > 0;
+
+    // source reads clamp to the visible w x h in all three planes
+    const int s = src[(size_t)min(y0 + ty, h - 1) * pitch + min(x0 + tx, w - 1)];
+    if (lt < 16) {
+      const int* lc = sh.lcol[pl];
+      int l = has_left ? lc[lt] : 128;
+      int lm = has_left ? lc[lt == 0 ? 0 : lt - 1] : 128;
+      int lp = has_left ? lc[lt == 15 ? 15 : lt + 1] : 128;
+      sh.lf[pl][lt] = (lm + 2 * l + lp + 2) >> 2;
+    }
+    if (tid < 4) sh.sad[tid] = 0;
+    __syncthreads();
+
+    const int l0 = has_left ? sh.lcol[pl][0] : 128;
+    const int lty = has_left ? sh.lcol[pl][ty] : 128;
+    const int l15 = has_left ? sh.lcol[pl][15] : 128;
+    const int lf = sh.lf[pl][ty];
+    int dc = 16 * l0 + 16;
+    for (int i = 0; i < 16; ++i) dc += has_left ? sh.lcol[pl][i] : 128;
+    dc >>= 5;
+
+    // ---- luma mode decision (chroma is DM): SAD over DC, H, V, Planar
+    if (luma) {
+      for (int m = 0; m < 4; ++m) {
+        int d = s - pred444(kModeOrder[m], true, tx, ty, l0, lty, l15, lf, dc);
+        d = d < 0 ? -d : d;
+        for (int off = 32; off; off >>= 1) d += __shfl_down(d, off, 64);
+        if ((tid & 63) == 0) atomicAdd(&sh.sad[m], d);
+      }
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int best = 0;
+      int bs = sh.sad[0];
+      for (int m = 1; m < 4; ++m)
+        if (sh.sad[m] < bs) {
+          bs = sh.sad[m];
+          best = m;
+        }
+      sh.best = best;
+    }
+    __syncthreads();
+    const int mode = kModeOrder[sh.best];
+    const int p = pred444(mode, luma, tx, ty, l0, lty, l15, lf, dc);
+    sh.res[pl][lt] = (short)(s - p);
+    __syncthreads();
+
+    // ---- forward T16 per plane: stage1 over columns, stage2 over rows
+    {
+      int acc = 0;
+      for (int y = 0; y < 16; ++y) acc += cT16[ty][y] * sh.res[pl][y * 16 + tx];
+      sh.tmp[pl][lt] = (acc + 4) >> 3;
+    }
+    __syncthreads();
+    {
+      int acc = 0;
+      for (int x = 0; x < 16; ++x)
+        acc += sh.tmp[pl][ty * 16 + x] * cT16[tx][x];
+      int coef = clip16d((acc + 512) >> 10);
+      const int qbits = 14 + q / 6 + 3;
+      const int add = 171 << (qbits - 9);
+      int a = coef < 0 ? -coef : coef;
+      int lv = (a * cQuantScale[q % 6] + add) >> qbits;
+      if (lv > 32767) lv = 32767;
+      if (coef < 0) lv = -lv;
+      sh.coef[pl][lt] = (short)lv;
+      if (tid == 0) sh.cbf = 0;
+    }
+    __syncthreads();
+    {
+      int nz = sh.coef[pl][lt] != 0;
+      if (__any(nz) && (tid & 63) == 0) atomicOr(&sh.cbf, 1 << pl);
+    }
+    __syncthreads();
+    const bool cbf_p = (sh.cbf >> pl) & 1;
+
+    const size_t ctu_base =
+        (size_t)(job.ctu_row * ctbw + cx) * kHevcLevelsPerCtu444;
+    levels[ctu_base + pl * 256 + lt] = sh.coef[pl][lt];
+
+    // ---- dequant + inverse + recon. cbf differs between planes, so the
+    // barriers sit at top level and the work is guarded per plane.
+    if (cbf_p) {
+      const int bd_shift = 7;
+      const long long scale =
+          ((long long)cDequantScale[q % 6] << (q / 6)) * 16;
+      long long d = ((long long)sh.coef[pl][lt] * scale +
+                     (1 << (bd_shift - 1))) >> bd_shift;
+      sh.tmp[pl][lt] = clip16d((int)d);
+    }
+    __syncthreads();
+    if (cbf_p) {
+      int acc = 0;
+      for (int u = 0; u < 16; ++u)
+        acc += cT16[u][ty] * sh.tmp[pl][u * 16 + tx];
+      sh.res[pl][lt] = (short)clip16d((acc + 64) >> 7);
+    }
+    __syncthreads();
+    int recon = p;
+    if (cbf_p) {
+      int acc = 0;
+      for (int v = 0; v < 16; ++v)
+        acc += sh.res[pl][ty * 16 + v] * cT16[v][tx];
+      recon = clip8d(p + clip16d((acc + 2048) >> 12));
+    }
+    cur[(size_t)(y0 + ty) * pitch + x0 + tx] = (uint8_t)recon;
+    if (tx == 15) sh.lcol[pl][ty] = recon;
+    if (tid == 0) {
+      meta[(size_t)(job.ctu_row * ctbw + cx) * kHevcMetaPerCtu + 0] = mode;
+      meta[(size_t)(job.ctu_row * ctbw + cx) * kHevcMetaPerCtu + 1] = sh.cbf;
+    }
+    __syncthreads();
+  }
+}
+
+void launch_hevc_rows444(const uint8_t* d_srcY, const uint8_t* d_srcCb,
+                         const uint8_t* d_srcCr, int pitch, int w, int h,
+                         uint8_t* d_curY, uint8_t* d_curCb, uint8_t* d_curCr,
+                         int ctbw, int n_jobs, const HevcJob* d_jobs,
+                         int16_t* d_levels, int* d_meta, hipStream_t stream) {
+  if (n_jobs == 0) return;
+  hipLaunchKernelGGL(k_hevc_rows444, dim3(n_jobs), dim3(768), 0, stream,
+                     d_srcY, d_srcCb, d_srcCr, pitch, w, h, d_curY, d_curCb,
+                     d_curCr, ctbw, d_jobs, d_levels, d_meta);
+}
+
 // ---- CABAC kernel --------------------------------------------------------
 // Scalar transliteration of native/cpu/hevc/{cabac.h,entropy.h}; one lane
 // per slice-segment job.
@@ -629,7 +823,11 @@ __constant__ uint8_t cSigPat[4][16] = {
 // wave lockstep — that costs ~64x with one job per LANE)
 #define CTX_LDS(i) ctx_lds[(i)]
 
-template <int N>
+//
+// kInst only separates instantiations: the 4:4:4 CTU coder calls <16, 1>
+// three times, and sharing <16, 0> with the 4:2:0 coder would change how
+// the compiler inlines it there (its scratch use was seen to move).
+template <int N, int kInst = 0>
 __device__ void dev_code_residual(DevCabac& cab, uint32_t* ctx_lds, int lane,
                                   const int16_t* __restrict__ level,
                                   int cidx) {
@@ -819,6 +1017,9 @@ __device__ void dev_code_residual(DevCabac& cab, uint32_t* ctx_lds, int lane,
   }
 }
 
+// F444: the chroma TBs are 16x16 at lv + 256 / lv + 512 (hevc_gpu_layout.h)
+// and go through the same dev_code_residual<16> as luma with cidx 1 / 2.
+template <bool F444>
 __device__ void dev_code_ctu(DevCabac& cab, uint32_t* ctx_lds, int lane,
                              int mode, int left_mode, int cbf_mask,
                              const int16_t* __restrict__ lv) {
@@ -868,11 +1069,20 @@ __device__ void dev_code_ctu(DevCabac& cab, uint32_t* ctx_lds, int lane,
   cab.bin(&CTX_LDS(HG_CTX_CBFC), (cbf_mask >> 1) & 1);
   cab.bin(&CTX_LDS(HG_CTX_CBFC), (cbf_mask >> 2) & 1);
   cab.bin(&CTX_LDS(HG_CTX_CBFY + 1), cbf_mask & 1);
-  if (cbf_mask & 1) dev_code_residual<16>(cab, ctx_lds, lane, lv, 0);
-  if (cbf_mask & 2) dev_code_residual<8>(cab, ctx_lds, lane, lv + 256, 1);
-  if (cbf_mask & 4) dev_code_residual<8>(cab, ctx_lds, lane, lv + 320, 2);
+  if (F444) {
+    if (cbf_mask & 1) dev_code_residual<16, 1>(cab, ctx_lds, lane, lv, 0);
+    if (cbf_mask & 2)
+      dev_code_residual<16, 1>(cab, ctx_lds, lane, lv + 256, 1);
+    if (cbf_mask & 4)
+      dev_code_residual<16, 1>(cab, ctx_lds, lane, lv + 512, 2);
+  } else {
+    if (cbf_mask & 1) dev_code_residual<16>(cab, ctx_lds, lane, lv, 0);
+    if (cbf_mask & 2) dev_code_residual<8>(cab, ctx_lds, lane, lv + 256, 1);
+    if (cbf_mask & 4) dev_code_residual<8>(cab, ctx_lds, lane, lv + 320, 2);
+  }
 }
 
+template <bool F444>
 __global__ __launch_bounds__(64) void k_hevc_cabac(
     const int16_t* __restrict__ levels, const int* __restrict__ meta,
     int ctbw, int n_jobs, const HevcJob* __restrict__ jobs,
@@ -914,8 +1124,9 @@ __global__ __launch_bounds__(64) void k_hevc_cabac(
     const size_t mbase = (size_t)(job.ctu_row * ctbw + cx);
     const int mode = meta[mbase * kHevcMetaPerCtu + 0];
     const int cbf = meta[mbase * kHevcMetaPerCtu + 1];
-    dev_code_ctu(cab, ctx_lds, lane, mode, left_mode, cbf,
-                 levels + mbase * kHevcLevelsPerCtu);
+    dev_code_ctu<F444>(
+        cab, ctx_lds, lane, mode, left_mode, cbf,
+        levels + mbase * (F444 ? kHevcLevelsPerCtu444 : kHevcLevelsPerCtu));
     left_mode = mode;
     cab.terminate(ci == job.seg_w - 1 ? 1 : 0);
   }
@@ -928,11 +1139,16 @@ __global__ __launch_bounds__(64) void k_hevc_cabac(
 void launch_hevc_cabac(const int16_t* d_levels, const int* d_meta, int ctbw,
                        int n_jobs, const HevcJob* d_jobs, uint8_t* d_out,
                        int out_stride_bytes, int* d_counts,
-                       hipStream_t stream) {
+                       hipStream_t stream, bool fullcolor) {
   if (n_jobs == 0) return;
-  hipLaunchKernelGGL(k_hevc_cabac, dim3(n_jobs), dim3(64), 0,
-                     stream, d_levels, d_meta, ctbw, n_jobs, d_jobs, d_out,
-                     out_stride_bytes, d_counts);
+  if (fullcolor)
+    hipLaunchKernelGGL(k_hevc_cabac<true>, dim3(n_jobs), dim3(64), 0,
+                       stream, d_levels, d_meta, ctbw, n_jobs, d_jobs, d_out,
+                       out_stride_bytes, d_counts);
+  else
+    hipLaunchKernelGGL(k_hevc_cabac<false>, dim3(n_jobs), dim3(64), 0,
+                       stream, d_levels, d_meta, ctbw, n_jobs, d_jobs, d_out,
+                       out_stride_bytes, d_counts);
 }
 
 }  // namespace hevcgpu

@@ -282,18 +282,22 @@ PYBIND11_MODULE(_native, m) {
   struct PyHevc {
     hevc::StripeEncoder enc;
     int w, h, ypitch, cpitch;
+    bool fullcolor;
     std::vector<uint8_t> yuv;
-    PyHevc(int width, int height, int slices_per_row)
-        : enc(width, height, slices_per_row), w(width), h(height) {
+    PyHevc(int width, int height, int slices_per_row, bool fc)
+        : enc(width, height, slices_per_row, fc), w(width), h(height),
+          fullcolor(fc) {
       ypitch = (width + 15) & ~15;
-      cpitch = ypitch / 2;
+      cpitch = fc ? ypitch : ypitch / 2;
       int yh = (height + 15) & ~15;
-      yuv.resize(static_cast<size_t>(ypitch) * yh * 3 / 2);
+      yuv.resize(fc ? static_cast<size_t>(ypitch) * yh * 3
+                    : static_cast<size_t>(ypitch) * yh * 3 / 2);
     }
   };
   py::class_<PyHevc>(m, "HevcEncoder")
-      .def(py::init<int, int, int>(), py::arg("width"), py::arg("height"),
-           py::arg("slices_per_row") = 1)
+      .def(py::init<int, int, int, bool>(), py::arg("width"),
+           py::arg("height"), py::arg("slices_per_row") = 1,
+           py::arg("fullcolor") = false)
       .def(
           "encode",
           [](PyHevc& self, py::buffer bgrx, int qp) {
@@ -307,10 +311,16 @@ PYBIND11_MODULE(_native, m) {
               uint8_t* y = self.yuv.data();
               int yh = (self.h + 15) & ~15;
               uint8_t* cb = y + static_cast<size_t>(self.ypitch) * yh;
-              uint8_t* cr = cb + static_cast<size_t>(self.cpitch) * (yh / 2);
-              h264::bgrx_to_yuv420(static_cast<const uint8_t*>(info.ptr),
-                                   self.w * 4, self.w, self.h, y, self.ypitch,
-                                   cb, cr, self.cpitch);
+              uint8_t* cr = cb + static_cast<size_t>(self.cpitch) *
+                                     (self.fullcolor ? yh : yh / 2);
+              if (self.fullcolor)
+                h264::bgrx_to_yuv444(static_cast<const uint8_t*>(info.ptr),
+                                     self.w * 4, self.w, self.h, y, cb, cr,
+                                     self.ypitch);
+              else
+                h264::bgrx_to_yuv420(static_cast<const uint8_t*>(info.ptr),
+                                     self.w * 4, self.w, self.h, y,
+                                     self.ypitch, cb, cr, self.cpitch);
               self.enc.encode_frame(y, self.ypitch, cb, cr, self.cpitch, qp,
                                     out, &st);
             }
@@ -325,12 +335,13 @@ PYBIND11_MODULE(_native, m) {
       .def("recon", [](PyHevc& self) {
         int yh = (self.h + 15) & ~15;
         int yp = self.enc.recon_ypitch(), cp = self.enc.recon_cpitch();
+        int chh = self.fullcolor ? yh : yh / 2;
         py::bytes y(reinterpret_cast<const char*>(self.enc.recon_y()),
                     static_cast<size_t>(yp) * yh);
         py::bytes cb(reinterpret_cast<const char*>(self.enc.recon_cb()),
-                     static_cast<size_t>(cp) * yh / 2);
+                     static_cast<size_t>(cp) * chh);
         py::bytes cr(reinterpret_cast<const char*>(self.enc.recon_cr()),
-                     static_cast<size_t>(cp) * yh / 2);
+                     static_cast<size_t>(cp) * chh);
         return py::make_tuple(y, cb, cr, yp, cp);
       });
 

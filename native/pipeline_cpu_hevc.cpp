@@ -23,6 +23,7 @@ class CpuHevcPipeline : public EncodePipeline {
                     const Emit& emit) override {
     const int stripe_h = std::max(16, settings_.stripe_height & ~15);
     size_t n_stripes = (frame.height + stripe_h - 1) / stripe_h;
+    const bool fc = settings_.video_fullcolor;
     if (encoders_.size() != n_stripes || frame.width != w_) {
       encoders_.clear();
       w_ = frame.width;
@@ -30,13 +31,14 @@ class CpuHevcPipeline : public EncodePipeline {
         int y0 = static_cast<int>(i) * stripe_h;
         int hgt = std::min(stripe_h, frame.height - y0);
         encoders_.push_back(std::make_unique<hevc::StripeEncoder>(
-            frame.width, hgt, hevc::default_slices_per_row(frame.width)));
+            frame.width, hgt, hevc::default_slices_per_row(frame.width), fc));
       }
       ypitch_ = (frame.width + 15) & ~15;
-      cpitch_ = ypitch_ / 2;
+      cpitch_ = fc ? ypitch_ : ypitch_ / 2;
       yuv_.resize(n_stripes);
       for (auto& v : yuv_)
-        v.resize(static_cast<size_t>(ypitch_) * stripe_h * 3 / 2);
+        v.resize(fc ? static_cast<size_t>(ypitch_) * stripe_h * 3
+                    : static_cast<size_t>(ypitch_) * stripe_h * 3 / 2);
     }
 
     struct Out {
@@ -56,10 +58,16 @@ class CpuHevcPipeline : public EncodePipeline {
         int hgt = j.y1 - j.y0;
         uint8_t* y = yuv_[i].data();
         uint8_t* cb = y + static_cast<size_t>(ypitch_) * stripe_h;
-        uint8_t* cr = cb + static_cast<size_t>(cpitch_) * (stripe_h / 2);
-        h264::bgrx_to_yuv420(
-            frame.data + static_cast<size_t>(j.y0) * frame.stride,
-            frame.stride, frame.width, hgt, y, ypitch_, cb, cr, cpitch_);
+        uint8_t* cr = cb + static_cast<size_t>(cpitch_) *
+                               (fc ? stripe_h : stripe_h / 2);
+        if (fc)
+          h264::bgrx_to_yuv444(
+              frame.data + static_cast<size_t>(j.y0) * frame.stride,
+              frame.stride, frame.width, hgt, y, cb, cr, ypitch_);
+        else
+          h264::bgrx_to_yuv420(
+              frame.data + static_cast<size_t>(j.y0) * frame.stride,
+              frame.stride, frame.width, hgt, y, ypitch_, cb, cr, cpitch_);
         encoders_[i]->encode_frame(y, ypitch_, cb, cr, cpitch_, ctx.crf,
                                    outs[i].bytes);
       });
@@ -90,11 +98,13 @@ class CpuHevcPipeline : public EncodePipeline {
     d.ypitch = e.recon_ypitch();
     d.cpitch = e.recon_cpitch();
     int yh = (e.height() + 15) & ~15;
+    // fullcolor recon chroma is full-size (cpitch == ypitch, yh rows)
+    int chh = settings_.video_fullcolor ? yh : yh / 2;
     d.y.assign(e.recon_y(), e.recon_y() + static_cast<size_t>(d.ypitch) * yh);
     d.cb.assign(e.recon_cb(),
-                e.recon_cb() + static_cast<size_t>(d.cpitch) * yh / 2);
+                e.recon_cb() + static_cast<size_t>(d.cpitch) * chh);
     d.cr.assign(e.recon_cr(),
-                e.recon_cr() + static_cast<size_t>(d.cpitch) * yh / 2);
+                e.recon_cr() + static_cast<size_t>(d.cpitch) * chh);
     return true;
   }
 

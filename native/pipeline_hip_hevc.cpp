@@ -22,8 +22,12 @@ namespace {
 
 class HipHevcPipeline : public EncodePipeline {
  public:
+  // CABAC output bytes reserved per fullcolor CTU (derivation in alloc_for)
+  static constexpr int kFullcolorBytesPerCtu = 4096;
+
   explicit HipHevcPipeline(const CaptureSettings& s)
-      : settings_(s), pool_(encode_pool_threads()), dev_(s.gpu_id) {
+      : settings_(s), pool_(encode_pool_threads()), dev_(s.gpu_id),
+        fc_(s.video_fullcolor) {
     cpu_entropy_ = std::getenv("HIPFLUX_CPU_HEVC_ENTROPY") != nullptr;
     timing_ = std::getenv("HIPFLUX_TIMES") != nullptr;
     stripe_h_ = std::max(16, s.stripe_height & ~15);
@@ -68,7 +72,7 @@ class HipHevcPipeline : public EncodePipeline {
                                rows_stream_));
     HIP_CHECK(hipEventRecord(ev_h2d_[par], rows_stream_));
     launch_bgrx_to_planes(d_frame_[par], w_, h_, frame.stride / 4, d_srcY_,
-                          d_srcCb_, d_srcCr_, ypitch_, cpitch_, false,
+                          d_srcCb_, d_srcCr_, ypitch_, cpitch_, fc_,
                           rows_stream_);
 
     // ---- job list (must mirror the CPU StripeEncoder's segmentation)
@@ -95,7 +99,7 @@ class HipHevcPipeline : public EncodePipeline {
           j.ctu_x0 = s0;
           j.seg_w = std::min(per, ctbw_ - s0);
           j.qp = qp;
-          j.qpc = hevc::chroma_qp(qp);
+          j.qpc = hevc::chroma_qp_for(qp, fc_);
           j.first_slice = (r == 0 && s0 == 0) ? 1 : 0;
           j.slice_addr = r * ctbw_ + s0;
           j.addr_bits = addr_bits;
@@ -114,10 +118,16 @@ class HipHevcPipeline : public EncodePipeline {
     HIP_CHECK(hipMemcpyAsync(d_jobs_[par], h_jobs_[par],
                              sizeof(hevcgpu::HevcJob) * n_jobs,
                              hipMemcpyHostToDevice, rows_stream_));
-    hevcgpu::launch_hevc_rows(d_srcY_, d_srcCb_, d_srcCr_, ypitch_, cpitch_,
-                              w_, h_, d_curY_, d_curCb_, d_curCr_, ctbw_,
-                              n_jobs, d_jobs_[par], d_levels_[par],
-                              d_meta_[par], rows_stream_);
+    if (fc_)
+      hevcgpu::launch_hevc_rows444(d_srcY_, d_srcCb_, d_srcCr_, ypitch_, w_,
+                                   h_, d_curY_, d_curCb_, d_curCr_, ctbw_,
+                                   n_jobs, d_jobs_[par], d_levels_[par],
+                                   d_meta_[par], rows_stream_);
+    else
+      hevcgpu::launch_hevc_rows(d_srcY_, d_srcCb_, d_srcCr_, ypitch_,
+                                cpitch_, w_, h_, d_curY_, d_curCb_, d_curCr_,
+                                ctbw_, n_jobs, d_jobs_[par], d_levels_[par],
+                                d_meta_[par], rows_stream_);
     HIP_CHECK(hipEventRecord(ev_rows_[par], rows_stream_));
     HIP_CHECK(hipStreamWaitEvent(stream_, ev_rows_[par], 0));
     if (cpu_entropy_) {
@@ -131,7 +141,7 @@ class HipHevcPipeline : public EncodePipeline {
     if (timing_) HIP_CHECK(hipEventRecord(ev_t_[1], stream_));
     hevcgpu::launch_hevc_cabac(d_levels_[par], d_meta_[par], ctbw_, n_jobs,
                                d_jobs_[par], d_out_[par], out_stride_,
-                               d_counts_[par], stream_);
+                               d_counts_[par], stream_, fc_);
     if (timing_) HIP_CHECK(hipEventRecord(ev_t_[2], stream_));
     HIP_CHECK(hipMemcpyAsync(h_counts_[par], d_counts_[par],
                              sizeof(int) * 3 * n_jobs,
@@ -185,7 +195,7 @@ class HipHevcPipeline : public EncodePipeline {
         o.vis_h = sr.vis_h;
         const int coded_h = (sr.vis_h + 15) & ~15;
         hevc::write_hevc_stripe_headers(ctbw_ * 16, coded_h, w_, sr.vis_h,
-                                        o.bytes);
+                                        o.bytes, fc_);
         for (int j = sr.job0; j < sr.jobn; ++j) {
           const auto& job = h_jobs_[par][j];
           if (cpu_entropy_) {
@@ -193,7 +203,7 @@ class HipHevcPipeline : public EncodePipeline {
                                       job.ctu_row, job.ctu_x0, job.seg_w,
                                       job.qp, job.first_slice != 0,
                                       job.slice_addr, job.addr_bits,
-                                      o.bytes);
+                                      o.bytes, fc_);
           } else {
             hevc::assemble_hevc_slice_nal(
                 h_out_[par] + (size_t)j * out_stride_,
@@ -261,8 +271,8 @@ class HipHevcPipeline : public EncodePipeline {
     d.cpitch = cpitch_;
     const int ch16 = (h_ + 15) & ~15;
     d.y.resize(static_cast<size_t>(ypitch_) * ch16);
-    d.cb.resize(static_cast<size_t>(cpitch_) * ch16 / 2);
-    d.cr.resize(static_cast<size_t>(cpitch_) * ch16 / 2);
+    d.cb.resize(static_cast<size_t>(cpitch_) * crows_);
+    d.cr.resize(static_cast<size_t>(cpitch_) * crows_);
     HIP_CHECK(hipMemcpy(d.y.data(), d_curY_, d.y.size(),
                         hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(d.cb.data(), d_curCb_, d.cb.size(),
@@ -290,20 +300,24 @@ class HipHevcPipeline : public EncodePipeline {
     ctbw_ = (w + 15) / 16;
     ctbh_ = (h + 15) / 16;
     ypitch_ = ctbw_ * 16;
-    cpitch_ = ypitch_ / 2;
     const int ch16 = ctbh_ * 16;
+    // fullcolor: full-size chroma source/recon planes
+    cpitch_ = fc_ ? ypitch_ : ypitch_ / 2;
+    crows_ = fc_ ? ch16 : ch16 / 2;
 
     for (int i = 0; i < 2; ++i)
       arena_.dev(d_frame_[i], static_cast<size_t>(w + 64) * 4 * (h + 16));
     arena_.dev(d_srcY_, static_cast<size_t>(ypitch_) * ch16);
-    arena_.dev(d_srcCb_, static_cast<size_t>(cpitch_) * ch16 / 2);
-    arena_.dev(d_srcCr_, static_cast<size_t>(cpitch_) * ch16 / 2);
+    arena_.dev(d_srcCb_, static_cast<size_t>(cpitch_) * crows_);
+    arena_.dev(d_srcCr_, static_cast<size_t>(cpitch_) * crows_);
     arena_.dev(d_curY_, static_cast<size_t>(ypitch_) * ch16);
-    arena_.dev(d_curCb_, static_cast<size_t>(cpitch_) * ch16 / 2);
-    arena_.dev(d_curCr_, static_cast<size_t>(cpitch_) * ch16 / 2);
+    arena_.dev(d_curCb_, static_cast<size_t>(cpitch_) * crows_);
+    arena_.dev(d_curCr_, static_cast<size_t>(cpitch_) * crows_);
 
     const size_t n_ctu = static_cast<size_t>(ctbw_) * ctbh_;
-    const size_t n_levels = n_ctu * hevcgpu::kHevcLevelsPerCtu;
+    const size_t n_levels =
+        n_ctu * (fc_ ? hevcgpu::kHevcLevelsPerCtu444
+                     : hevcgpu::kHevcLevelsPerCtu);
     const size_t n_meta = n_ctu * hevcgpu::kHevcMetaPerCtu;
     levels_bytes_ = n_levels * sizeof(int16_t);
     meta_bytes_ = n_meta * sizeof(int);
@@ -318,6 +332,12 @@ class HipHevcPipeline : public EncodePipeline {
     // (384) x a handful of bypass bytes; 2 KB/CTU is a safe ceiling
     const int per = (ctbw_ + spr - 1) / spr;
     out_stride_ = per * 2048;
+    // fullcolor codes 768 coefficients per CTU, so that argument does not
+    // carry over. Measured on the CPU encoder at qp 0 (make asan-hevc444),
+    // largest slice-segment bytes per CTU over 60-, 8- and 1-CTU segments:
+    // uniform noise 1179, saturated 1-pixel checkerboard 500. The stride
+    // is 2x the larger figure rounded up to a power of two.
+    if (fc_) out_stride_ = per * kFullcolorBytesPerCtu;
     for (int i = 0; i < 2; ++i) {
       arena_.dev(d_jobs_[i], max_jobs);
       arena_.dev(d_out_[i], max_jobs * out_stride_);
@@ -345,11 +365,13 @@ class HipHevcPipeline : public EncodePipeline {
   CompactReadback<uint8_t> readback_;   // CABAC bytes per slice
   bool cpu_entropy_ = false;
   bool timing_ = false;
+  const bool fc_;         // video_fullcolor: Main 4:4:4 instead of 4:2:0
   int stripe_h_ = 64;
   int depth_ = 1;         // 1 = sync (latency mode), 2 = pipelined
   int parity_ = 0;
   Pending prev_;
   int w_ = 0, h_ = 0, ctbw_ = 0, ctbh_ = 0, ypitch_ = 0, cpitch_ = 0;
+  int crows_ = 0;         // rows of one chroma plane
   int out_stride_ = 0;
   size_t levels_bytes_ = 0, meta_bytes_ = 0;
 

@@ -180,7 +180,9 @@ SETTING_DEFINITIONS: list[SettingDef] = [
     SettingDef("keyframe_interval_s", float, 0.0,
                "Seconds between forced IDR frames; 0 = infinite GOP (on-demand IDR only).",
                value_range=(0.0, 600.0)),
-    SettingDef("video_fullcolor", bool, False, "4:4:4 chroma (I444) instead of 4:2:0.",
+    SettingDef("video_fullcolor", bool, False,
+               "4:4:4 chroma (I444) instead of 4:2:0: JPEG, H.264 (Hi444) "
+               "and HEVC (Main 4:4:4).",
                client=True),
     SettingDef("video_pipeline_depth", int, 1,
                "Encoder frame pipelining depth: 1 = synchronous (lowest "

@@ -60,6 +60,33 @@ class H264Row {
   }
 }
 
+/* hevcCodecString:begin (pure; tests/hevc444 evaluates this block in node) */
+/* WebCodecs codec string for an HEVC key stripe, chosen from the stream.
+ *
+ * The stripe starts with the VPS: 4-byte start code, 2-byte NAL header,
+ * 4 fixed VPS bytes (ids/flags, then 0xFFFF), then profile_tier_level.
+ * general_profile_idc is the low 5 bits of byte 10; none of the bytes
+ * before it can be 00 00 0x, so no emulation prevention precedes it.
+ *
+ * ISO/IEC 14496-15 Annex E: hev1.<profile_idc>.<compatibility flags,
+ * bit-reversed, hex>.<tier L|H><level_idc>.<constraint bytes in hex,
+ * trailing zero bytes dropped>.
+ *  Main: profile 1; flags 1 and 2 set (0x60000000) reverse to 0x6; the
+ *    first constraint byte is progressive 1, interlaced 0, non_packed 1,
+ *    frame_only 1, then four zero bits = 1011 0000 = B0; the rest is 0.
+ *  Main 4:4:4: profile 4; flag 4 (0x08000000) reverses to 0x10; the
+ *    first byte continues with max_12bit 1, max_10bit 1, max_8bit 1,
+ *    max_422chroma 0 = 1011 1110 = BE; the second is max_420chroma 0,
+ *    max_monochrome 0, intra 0, one_picture_only 0, lower_bit_rate 1,
+ *    three zero bits = 0000 1000 = 8; the rest is 0.
+ * The level stays at 4.1 (L123) as before: decoders take the real level
+ * from the in-band parameter sets. */
+function hevcCodecString(payload) {
+  const profileIdc = payload.length > 10 ? payload[10] & 0x1f : 1;
+  return profileIdc === 4 ? "hev1.4.10.L123.BE.8" : "hev1.1.6.L123.B0";
+}
+/* hevcCodecString:end */
+
 const h264Rows = new Map();   // y -> H264Row
 let jpegDrawQueue = Promise.resolve();
 
@@ -79,8 +106,11 @@ function onBinary(buf) {
     const w = (d[6] << 8) | d[7];
     const h = (d[8] << 8) | d[9];
     ensureCanvas(w, y + h);
-    // 0x06 = HEVC Main (WebCodecs hev1 codec string); per-row decoders
-    const codec = tag === 0x06 ? "hev1.1.6.L123.B0" : "avc1.42e028";
+    // 0x06 = HEVC, Main or Main 4:4:4 (video_fullcolor); per-row decoders.
+    // Delta stripes never occur for HEVC (all-intra), so every stripe
+    // carries its VPS and names its own profile.
+    const codec = tag === 0x06 ? hevcCodecString(d.subarray(10))
+                               : "avc1.42e028";
     let row = h264Rows.get(y);
     if (!row || row.codec !== codec) {
       row = new H264Row(y, codec); h264Rows.set(y, row);

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""H.264 fullcolor (Hi444 separate colour planes) against 4:2:0, same
-process, same frames, alternating the two modes.
+"""Fullcolor (4:4:4) against 4:2:0 on a video pipeline, same process,
+same frames, alternating the two modes: H.264 (Hi444 separate colour
+planes, --output-mode 1, the default) or HEVC (Main 4:4:4,
+--output-mode 2).
 
     python tools/bench_fullcolor.py --kind gpu --width 1920 --height 1080 \\
-        --depth 1 --steps 600 --repeats 3
+        --depth 1 --steps 600 --repeats 3 [--output-mode 2]
 
 Both modes run through _native.BenchPipeline on worst-case input (every
 pixel of every frame random). One repeat is a timed window of --steps
@@ -41,6 +43,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--qp", type=int, default=28)
+    ap.add_argument("--output-mode", type=int, default=1, choices=[1, 2],
+                    help="1 = H.264 (default), 2 = HEVC")
     args = ap.parse_args()
 
     gpu = args.kind == "gpu"
@@ -72,10 +76,12 @@ def main():
     pipes = {}
     for mode, fc in (("fullcolor", True), ("420", False)):
         p = _native.BenchPipeline(args.kind, args.width, args.height,
-                                  qp=args.qp, stripe_height=64, output_mode=1,
+                                  qp=args.qp, stripe_height=64,
+                                  output_mode=args.output_mode,
                                   gpu_id=0 if gpu else -1,
                                   pipeline_depth=args.depth, fullcolor=fc)
-        want = "hip-h264" if gpu else "cpu-h264"
+        codec = "h264" if args.output_mode == 1 else "hevc"
+        want = f"hip-{codec}" if gpu else f"cpu-{codec}"
         if p.pipeline != want:
             sys.exit(f"bench_fullcolor: {mode} runs on {p.pipeline}, "
                      f"not {want}")
@@ -119,12 +125,14 @@ def main():
             r = window(mode)
             results[mode].append(r)
             print(json.dumps(dict(r, rep=rep, kind=args.kind,
-                                  depth=args.depth)), flush=True)
+                                  depth=args.depth,
+                                  output_mode=args.output_mode)), flush=True)
 
     def med(mode, key):
         return statistics.median(r[key] for r in results[mode])
 
-    summary = {"kind": args.kind, "width": args.width, "height": args.height,
+    summary = {"kind": args.kind, "output_mode": args.output_mode,
+               "width": args.width, "height": args.height,
                "depth": args.depth, "steps": args.steps,
                "repeats": args.repeats, "qp": args.qp}
     for mode in ("fullcolor", "420"):
