@@ -80,6 +80,9 @@ std::unique_ptr<EncodePipeline> make_cpu_h264_pipeline(const CaptureSettings&);
 std::unique_ptr<EncodePipeline> make_cpu_hevc_pipeline(const CaptureSettings&);
 // GPU (HIP/gfx950) pipeline; returns nullptr if no usable HIP device.
 std::unique_ptr<EncodePipeline> make_hip_pipeline(const CaptureSettings&);
+// CABAC output bytes the HIP HEVC pipeline reserves per CTU of a slice
+// segment (4:2:0 or fullcolor).
+int hip_hevc_bytes_per_ctu(bool fullcolor);
 
 class ScreenCapture {
  public:

@@ -1242,5 +1242,9 @@ PYBIND11_MODULE(_native, m) {
 
   m.def("hip_device_count", &hip_device_count,
         "Number of usable HIP devices (0 on CPU-only hosts).");
+  // HIP HEVC CABAC output stride per CTU (read-only; the stride-premise
+  // test compares measured slice sizes with these)
+  m.attr("HEVC_BYTES_PER_CTU") = hip_hevc_bytes_per_ctu(false);
+  m.attr("HEVC_FULLCOLOR_BYTES_PER_CTU") = hip_hevc_bytes_per_ctu(true);
   m.def("__version__", [] { return "0.1.0"; });
 }

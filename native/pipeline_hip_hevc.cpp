@@ -22,7 +22,9 @@ namespace {
 
 class HipHevcPipeline : public EncodePipeline {
  public:
-  // CABAC output bytes reserved per fullcolor CTU (derivation in alloc_for)
+  // CABAC output bytes reserved per CTU, 4:2:0 and fullcolor (derivation
+  // in alloc_for); hip_hevc_bytes_per_ctu() shows both to the tests
+  static constexpr int kBytesPerCtu = 2048;
   static constexpr int kFullcolorBytesPerCtu = 4096;
 
   explicit HipHevcPipeline(const CaptureSettings& s)
@@ -328,10 +330,14 @@ class HipHevcPipeline : public EncodePipeline {
 
     const int spr = hevc::default_slices_per_row(w);
     const size_t max_jobs = static_cast<size_t>(ctbh_) * spr + 8;
-    // worst-case CABAC bytes per CTU is bounded by the coefficient count
-    // (384) x a handful of bypass bytes; 2 KB/CTU is a safe ceiling
+    // DevCabac::put has no bound, so the stride has to hold the largest
+    // slice segment. Measured on the CPU encoder at qp 0, largest IDR NAL
+    // bytes per CTU over 1-, 8- and 20-CTU segments (profiles/NOTES.md,
+    // tests/test_hevc_recon_host.py): uniform noise 500, saturated 2x2
+    // colour checker 247, 1-pixel 0/255 checkerboard 169. The stride is
+    // at least 2x the largest figure, which the host test asserts.
     const int per = (ctbw_ + spr - 1) / spr;
-    out_stride_ = per * 2048;
+    out_stride_ = per * kBytesPerCtu;
     // fullcolor codes 768 coefficients per CTU, so that argument does not
     // carry over. Measured on the CPU encoder at qp 0 (make asan-hevc444),
     // largest slice-segment bytes per CTU over 60-, 8- and 1-CTU segments:
@@ -396,6 +402,11 @@ class HipHevcPipeline : public EncodePipeline {
 std::unique_ptr<EncodePipeline> make_hip_hevc_pipeline(
     const CaptureSettings& s) {
   return std::make_unique<HipHevcPipeline>(s);
+}
+
+int hip_hevc_bytes_per_ctu(bool fullcolor) {
+  return fullcolor ? HipHevcPipeline::kFullcolorBytesPerCtu
+                   : HipHevcPipeline::kBytesPerCtu;
 }
 
 }  // namespace hipflux

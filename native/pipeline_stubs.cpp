@@ -18,6 +18,7 @@ std::unique_ptr<EncodePipeline> make_cpu_h264_pipeline(
 std::unique_ptr<EncodePipeline> make_hip_pipeline(const CaptureSettings&) {
   return nullptr;
 }
+int hip_hevc_bytes_per_ctu(bool) { return 0; }
 #endif
 
 }  // namespace hipflux

@@ -1,6 +1,6 @@
 """From-spec decoder for the encoder's Main 4:4:4 streams (H.265 v2+).
 
-Subclasses tests/hevc_ref_decoder.py (imported unchanged) and overrides
+Subclasses tests/hevc_ref_decoder.py (same arithmetic) and overrides
 only what chroma_format_idc == 3 changes; a 4:2:0 stream falls through to
 the parent at every step. The rules, with their spec anchors:
 
@@ -45,17 +45,13 @@ def filter_flag(mode, n):
 class Decoder444(hrd.Decoder):
     """hrd.Decoder that also decodes chroma_format_idc == 3.
 
-    `ctus` records (mode, cbf_y, cbf_cb, cbf_cr) per decoded CTU and
-    `qpc_used` every chroma QP a slice was decoded with. `qpc_override`
-    (a function qp -> qpc) replaces the spec's chroma QP, for tests that
-    show a wrong mapping does not reproduce the encoder's recon."""
+    `ctus`, `qpc_used` and `qpc_override` are the parent's. Each slice and
+    CTU is decoded either here (4:4:4) or by the parent (4:2:0), never
+    both, so each is recorded once."""
 
     def __init__(self, qpc_override=None):
-        super().__init__()
-        self.ctus = []
-        self.qpc_used = []
+        super().__init__(qpc_override)
         self.ptl = None
-        self.qpc_override = qpc_override
 
     # ---- parameter sets ---------------------------------------------------
 

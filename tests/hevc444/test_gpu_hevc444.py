@@ -20,6 +20,7 @@ pytestmark = pytest.mark.gpu
 hipflux = pytest.importorskip("hipflux")
 from hipflux import _native
 from hevc444_ref_decoder import Decoder444
+from pipeline_content import frames_for
 
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(
     os.path.abspath(__file__))))
@@ -28,36 +29,6 @@ REPO = os.path.dirname(os.path.dirname(os.path.dirname(
 def require_gpu():
     if hipflux.hip_device_count() == 0:
         pytest.fail("gpu test ran on a host with no HIP device")
-
-
-@functools.lru_cache(maxsize=None)
-def frames_for(w, h, n, seed=42):
-    """Gradient + noise band + a moving saturated box + 1-pixel
-    alternating-chroma columns; built once per shape, never modified."""
-    rng = np.random.default_rng(seed)
-    base = np.zeros((h, w, 4), np.uint8)
-    base[:, :, 0] = np.linspace(0, 255, w, dtype=np.uint8)[None, :]
-    base[:, :, 1] = np.linspace(0, 255, h, dtype=np.uint8)[:, None]
-    base[:, :, 2] = 80
-    base[:, :, 3] = 255
-    band = max(1, min(16, h // 4))
-    base[h // 2:h // 2 + band, :, :3] = rng.integers(
-        0, 256, (band, w, 3), dtype=np.uint8)
-    c0 = w // 2
-    n_alt = min(24, w - c0)
-    odd = np.arange(n_alt) & 1
-    base[:, c0:c0 + n_alt, 0] = np.where(odd, 255, 0)[None, :]
-    base[:, c0:c0 + n_alt, 2] = np.where(odd, 0, 255)[None, :]
-    out = []
-    for i in range(n):
-        f = base.copy()
-        if w > 64 and h > 48:
-            x = (16 + i * 24) % (w - 48)
-            f[16:48, x:x + 48, 0] = 255
-            f[16:48, x:x + 48, 2] = 0
-        f.setflags(write=False)
-        out.append(f)
-    return tuple(out)
 
 
 @functools.lru_cache(maxsize=None)

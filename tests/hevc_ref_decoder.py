@@ -520,11 +520,20 @@ def decode_residual(cab, ctxs, n, cidx):
 
 
 class Decoder:
-    """Decode one independent HEVC stream (VPS/SPS/PPS + IDR pictures)."""
+    """Decode one independent HEVC stream (VPS/SPS/PPS + IDR pictures).
 
-    def __init__(self):
+    `ctus` records (mode, cbf_y, cbf_cb, cbf_cr) per decoded CTU, in
+    decode order, and `qpc_used` the chroma QP of every slice decoded.
+    `qpc_override` (a function qp -> qpc) replaces the spec's chroma QP,
+    for tests that show a wrong mapping does not reproduce the encoder's
+    recon. Without it the chroma QP is this module's own chroma_qp."""
+
+    def __init__(self, qpc_override=None):
         self.sps = None
         self.frames = []
+        self.ctus = []
+        self.qpc_used = []
+        self.qpc_override = qpc_override
 
     def decode(self, data):
         self.frames = []
@@ -618,6 +627,9 @@ class Decoder:
         cab = Cabac(br)
         ctxs = Contexts(qp)
         qpc = chroma_qp(qp)
+        if self.qpc_override is not None:
+            qpc = self.qpc_override(qp)
+        self.qpc_used.append(qpc)
         ctb_w = s["ctb_w"]
         caddr = addr
         left_mode = None   # luma mode of the CTU to the left (same slice)
@@ -667,6 +679,7 @@ class Decoder:
         cbf_cb = cab.decision(ctxs.cbf_chroma[0])
         cbf_cr = cab.decision(ctxs.cbf_chroma[0])
         cbf_y = cab.decision(ctxs.cbf_luma[1])
+        self.ctus.append((mode, cbf_y, cbf_cb, cbf_cr))
 
         avail = {"left": left_mode is not None, "top": False,
                  "top_right": False, "below_left": False, "corner": False}

@@ -45,12 +45,15 @@ _register(Suite(
     "codecs", "Entropy/transform conformance vs the from-spec decoders "
     "(H.264, HEVC, JPEG, Opus)", 0,
     ("test_h264.py", "test_h264_content.py", "test_h264_seg_plan.py",
-     "test_hevc.py", "test_jpeg.py", "test_opus.py", "test_opus_js.py",
-     "test_rate_control.py")))
+     "test_hevc.py", "test_hevc_recon_host.py", "test_jpeg.py",
+     "test_opus.py", "test_opus_js.py", "test_rate_control.py",
+     "fullcolor/test_h264_fullcolor_host.py",
+     "hevc444/test_hevc444_host.py")))
 _register(Suite(
     "engine", "Capture engine, damage, scaling, audio engine, recording",
     0, ("test_engine.py", "test_engine_h264.py", "test_audio.py",
-        "test_recording.py", "test_cursor.py", "test_watermark.py")))
+        "test_recording.py", "test_cursor.py", "test_watermark.py",
+        "frontend/test_frontend_host.py")))
 _register(Suite(
     "protocol", "Wire protocol, relay backpressure, settings, fuzzing",
     0, ("test_protocol.py", "test_relay.py", "test_settings.py",
@@ -72,12 +75,16 @@ _register(Suite(
     1, ("test_tile_comm.py",)))
 _register(Suite(
     "sanitize", "ASan/UBSan native harness + packaging lint", 1,
-    ("test_sanitizer.py",)))
+    ("test_sanitizer.py", "hevc444/test_hevc444_sanitizer.py")))
 _register(Suite(
     "gpu", "Byte-identity + numerics on a real MI355X", 2,
     ("test_gpu_h264.py", "test_gpu_h264_recon.py", "test_gpu_hevc.py",
-     "test_gpu_jpeg.py", "test_gpu_pipeline_host.py",
-     "test_gpu_tile_comm.py"), marker="gpu"))
+     "test_gpu_hevc_recon.py", "test_gpu_jpeg.py",
+     "test_gpu_pipeline_host.py", "test_gpu_tile_comm.py",
+     "frontend/test_gpu_frontend.py",
+     "frontend/test_gpu_frontend_engine.py",
+     "fullcolor/test_gpu_h264_fullcolor.py",
+     "hevc444/test_gpu_hevc444.py"), marker="gpu"))
 _register(Suite(
     "perf", "Bench contract guards (driver JSON line shape)", 3,
     ("test_bench_contract.py",)))

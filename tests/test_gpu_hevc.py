@@ -19,6 +19,7 @@ pytestmark = pytest.mark.gpu
 hipflux = pytest.importorskip("hipflux")
 from hipflux import _native
 from hevc_ref_decoder import Decoder
+from pipeline_content import assert_planes_equal, dump_planes
 
 
 def require_gpu():
@@ -105,11 +106,16 @@ def test_gpu_stream_decodes_bit_exact():
     require_gpu()
     w, h, n = 320, 192, 3
     frames = make_frames(w, h, n)
-    rows = flatten(encode("gpu", frames, w, h, 26))
+    out, dump = _native._pipeline_encode("gpu", frames, w, h, 26, 64, 2, True)
+    rows = flatten(out)
     for y, stream in rows.items():
         decoded = Decoder().decode(stream)
         assert len(decoded) == n
-    # fidelity spot check on the last frame's top stripe
+        # the kernel's recon planes hold the last frame: equal to what
+        # the decoder makes of it, in all three planes
+        assert_planes_equal(dump_planes(dump, h), y, decoded[-1],
+                            f"stripe y={y}")
+    # and the recon resembles the source (last frame's top stripe)
     dy = Decoder().decode(rows[0])[-1][0]
     src_y, _, _ = _native.bgrx_to_yuv420(frames[-1].tobytes(), w, h)
     src = np.frombuffer(src_y, np.uint8).reshape(h, w)[:64]

@@ -1,10 +1,8 @@
 """Host side of the three HIP pipelines (JPEG, H.264, HEVC) on a real
 MI355X: frame pipelining, re-allocation on a resolution change, frame
-upload from buffers whose addresses get reused, and the H.264 segment
-plan override. Every comparison is byte equality of emitted stripes."""
-
-import contextlib
-import os
+upload from buffers whose addresses get reused, the H.264 segment plan
+override, and the H.264 compacted read-back outgrowing its cap. Every
+comparison is byte equality of emitted stripes."""
 
 import numpy as np
 import pytest
@@ -13,7 +11,8 @@ pytestmark = pytest.mark.gpu
 
 hipflux = pytest.importorskip("hipflux")
 from hipflux import _native
-from h264_ref_decoder import Decoder
+from h264_ref_decoder import Decoder, split_nals
+from pipeline_content import env_vars, flat_and_mix
 
 STRIPE_H = 64
 # (id, output_mode, qp / jpeg quality)
@@ -23,22 +22,6 @@ CODECS = [("jpeg", 0, 60), ("h264", 1, 26), ("hevc", 2, 26)]
 def require_gpu():
     if hipflux.hip_device_count() == 0:
         pytest.fail("gpu test ran on a host with no HIP device")
-
-
-@contextlib.contextmanager
-def env_vars(**kv):
-    """Set environment knobs around a pipeline construction (they are
-    read when the pipeline is built) and restore them afterwards."""
-    old = {k: os.environ.get(k) for k in kv}
-    os.environ.update({k: str(v) for k, v in kv.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def fresh_frame(w, h, seed):
@@ -172,3 +155,38 @@ def test_h264_segs_override_without_exact_split_is_normalised():
         decoded = Decoder().decode(stream)
         assert len(decoded) == n
         assert decoded[0][0].shape[1] == w
+
+
+# ---- H.264 read-back growth ---------------------------------------------------
+
+def test_h264_readback_growth_refetches_whole_slices():
+    """Flat, flat, mix, flat, mix (mix: noise in the first 16 rows) with
+    one frame in flight and without. A frame leaves the compacted
+    read-back a cap of 2 * max + 64 words per slice; each noise frame's
+    first slice outgrows the cap of the frame before it and is fetched
+    again in full. (The JPEG and HEVC uses of the same helper:
+    test_gpu_readback_growth_refetches_whole_rows in test_gpu_jpeg.py,
+    test_readback_growth in test_gpu_hevc_recon.py.)"""
+    require_gpu()
+    w, h, stripe_h, qp = 256, 96, 48, 24
+    flat, mix = flat_and_mix(w, h)
+    frames = [flat, flat, mix, flat, mix]
+    runs = [per_frame_bytes(_native._pipeline_encode(
+        "gpu", frames, w, h, qp, stripe_h, 1, pipeline_depth=d))
+        for d in (2, 1)]
+    # the premise, in 32-bit words per emitted slice NAL
+    words = [[(len(n) + 3) // 4 + 1 for y, d in fr for n in split_nals(d)
+              if n[0] & 0x1F in (1, 5)] for fr in runs[0]]
+    print("slice words per frame:", words)
+    assert all(len(ws) == h // 16 for ws in words)
+    for noise in (2, 4):
+        assert max(words[noise]) > 2 * max(words[noise - 1]) + 64
+    assert len(runs[0]) == len(runs[1]) == len(frames)
+    for fi in range(len(frames)):
+        assert [y for y, _ in runs[0][fi]] == [0, 48]
+        assert runs[0][fi] == runs[1][fi], f"frame {fi}: depth 2 differs"
+    for y0 in (0, 48):
+        stream = b"".join(d for fr in runs[0] for y, d in fr if y == y0)
+        decoded = Decoder().decode(stream)
+        assert len(decoded) == len(frames)
+        assert decoded[0][0].shape == (48, w)

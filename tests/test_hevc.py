@@ -172,6 +172,7 @@ def test_odd_dimensions_cropping():
     ey, ecb, ecr = recon_planes(enc, w, h)
     assert np.array_equal(dy, ey)
     assert np.array_equal(dcb, ecb)
+    assert np.array_equal(dcr, ecr)
 
 
 def test_multiple_slices_per_row():

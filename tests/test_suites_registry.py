@@ -1,5 +1,6 @@
 """The suite registry must stay truthful: every referenced file exists,
-every test file belongs to a suite (reference tests/suites.py tiering)."""
+every test file, in tests/ or a directory below it, belongs to a suite
+(reference tests/suites.py tiering)."""
 
 import pathlib
 
@@ -14,7 +15,8 @@ def test_all_suite_paths_exist():
 
 def test_every_test_file_is_registered():
     registered = {p for s in suites.SUITES.values() for p in s.paths}
-    on_disk = {p.name for p in suites.TESTS_DIR.glob("test_*.py")}
+    on_disk = {p.relative_to(suites.TESTS_DIR).as_posix()
+               for p in suites.TESTS_DIR.rglob("test_*.py")}
     missing = on_disk - registered - {"test_suites_registry.py"}
     assert not missing, f"unregistered test files: {sorted(missing)}"
 
