@@ -20,9 +20,14 @@ constexpr int kChromaDcOff = 272;
 constexpr int kChromaAcOff = 280;
 
 // per-MB meta (2 x int32):
-//   m0: mode(2) | luma_mode<<2 | chroma_mode<<5  (mode: 0 skip, 1 inter,
-//       2 intra)
-//   m1: mvx (int16, quarter-pel) | mvy<<16
+//   m0: mode(2) | luma_mode<<2 (intra) | (hintx+64)<<8 | (hinty+64)<<15 |
+//       hopeless<<22  (mode: 0 skip, 1 inter, 2 intra). Hint and hopeless
+//       are the motion search's state from frame to frame; the row
+//       kernels keep bits 8..22 when they rewrite an intra MB of a P
+//       slice and clear them in an I slice. Zero is NOT "no hint": it
+//       reads as (-64,-64), clamped to (-48,-48) (docs/design.md).
+//   m1: mvx (int16, quarter-pel) | mvy<<16 for skip/inter MBs; the intra
+//       chroma mode otherwise
 constexpr int kMetaPerMb = 2;
 
 enum MbMode : int { kSkip = 0, kInter = 1, kIntra = 2 };

@@ -8,8 +8,11 @@
 namespace hipflux {
 namespace h264gpu {
 
+// 2x2 box average of the sw x sh plane; reads clamp to the rw x rh extent
+// that holds valid samples
 void launch_downsample2(const uint8_t* src, int spitch, int sw, int sh,
-                        uint8_t* dst, int dpitch, hipStream_t stream);
+                        int rw, int rh, uint8_t* dst, int dpitch,
+                        hipStream_t stream);
 
 void launch_h264_me(const uint8_t* srcY, int ypitch, int w, int h,
                     const uint8_t* refY, const uint8_t* srcY2,

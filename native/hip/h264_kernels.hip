@@ -1004,14 +1004,17 @@ __global__ void __launch_bounds__(64) k_h264_me_mfma(
     // this MB at quarter res: 4x4 proxy block
     const int qx0 = x0 >> 2, qy0 = y0 >> 2;
     const int qw = frame_w_mb16 >> 2;
+    // proxy rows and columns clamp to the last quarter-res sample whose
+    // 4x4 footprint lies inside the picture (sample 0 for a picture under
+    // 4 rows or columns; the pyramid itself is built from clamped reads)
+    const int qr_max = max(0, (h >> 2) - 1), qc_max = max(0, (w >> 2) - 1);
     const int qs_y0 = job.stripe_y0 >> 2, qs_y1 = job.stripe_y1 >> 2;
     int px[4];
     {
       int rr = lane & 3;
-      const uint8_t* sr = srcY2 + (size_t)min(qy0 + rr, (h >> 2) - 1) *
-                                      ypitch2;
+      const uint8_t* sr = srcY2 + (size_t)min(qy0 + rr, qr_max) * ypitch2;
       for (int j = 0; j < 4; ++j)
-        px[j] = sr[min(qx0 + j, qw - 1)];
+        px[j] = sr[min(qx0 + j, qc_max)];
     }
     int bs = INT_MAX, bmx2 = 0, bmy2 = 0;
     // 25x25 candidates, distributed over lanes (lane covers cands with
@@ -1191,26 +1194,32 @@ void launch_h264_rows(const uint8_t* srcY, const uint8_t* srcCb,
 
 // ---------------------------------------------------------------------------
 // 2x2 box downsample (luma pyramid for ME acquisition). One thread per
-// output pixel.
+// output pixel. The source holds valid samples only in [0, rw) x [0, rh);
+// reads clamp to that extent, so the output over the whole sw x sh plane
+// is the box average of the edge-replicated picture and depends on
+// nothing else.
 __global__ void k_downsample2(const uint8_t* __restrict__ src, int spitch,
-                              int sw, int sh, uint8_t* __restrict__ dst,
-                              int dpitch) {
+                              int sw, int sh, int rw, int rh,
+                              uint8_t* __restrict__ dst, int dpitch) {
   int x = blockIdx.x * blockDim.x + threadIdx.x;
   int y = blockIdx.y * blockDim.y + threadIdx.y;
   int dw = sw >> 1, dh = sh >> 1;
   if (x >= dw || y >= dh) return;
-  const uint8_t* r0 = src + (size_t)(2 * y) * spitch + 2 * x;
-  const uint8_t* r1 = r0 + spitch;
+  const int xa = max(0, min(2 * x, rw - 1));
+  const int xb = max(0, min(2 * x + 1, rw - 1));
+  const uint8_t* r0 = src + (size_t)max(0, min(2 * y, rh - 1)) * spitch;
+  const uint8_t* r1 = src + (size_t)max(0, min(2 * y + 1, rh - 1)) * spitch;
   dst[(size_t)y * dpitch + x] =
-      (uint8_t)((r0[0] + r0[1] + r1[0] + r1[1] + 2) >> 2);
+      (uint8_t)((r0[xa] + r0[xb] + r1[xa] + r1[xb] + 2) >> 2);
 }
 
 void launch_downsample2(const uint8_t* src, int spitch, int sw, int sh,
-                        uint8_t* dst, int dpitch, hipStream_t stream) {
+                        int rw, int rh, uint8_t* dst, int dpitch,
+                        hipStream_t stream) {
   dim3 b(16, 16);
   dim3 g(((sw >> 1) + 15) / 16, ((sh >> 1) + 15) / 16);
   hipLaunchKernelGGL(k_downsample2, g, b, 0, stream, src, spitch, sw, sh,
-                     dst, dpitch);
+                     rw, rh, dst, dpitch);
 }
 
 }  // namespace h264gpu

@@ -180,15 +180,20 @@ class HipH264Pipeline : public EncodePipeline {
       uint8_t* src2 = d_srcY2_ + pl * pyr_stride_;
       uint8_t* ref2 = d_refY2_ + pl * pyr_stride_;
       if (!ctx.idr) {
-        h264gpu::launch_downsample2(src, ypitch_, ypitch_, mbh_ * 16,
-                                    d_mip1_, ypitch_ / 2, rows_stream_);
-        h264gpu::launch_downsample2(d_mip1_, ypitch_ / 2, ypitch_ / 2,
-                                    mbh_ * 8, src2, ypitch_ / 4,
+        // the CSC writes only the w_ x h_ picture: the first source level
+        // clamps its reads there (edge replication, the rule the full-
+        // resolution source reads follow); every other level reads a
+        // fully written MB-aligned plane
+        const int pw = ypitch_, ph = mbh_ * 16;
+        h264gpu::launch_downsample2(src, ypitch_, pw, ph, w_, h_, d_mip1_,
+                                    ypitch_ / 2, rows_stream_);
+        h264gpu::launch_downsample2(d_mip1_, ypitch_ / 2, pw / 2, ph / 2,
+                                    pw / 2, ph / 2, src2, ypitch_ / 4,
                                     rows_stream_);
-        h264gpu::launch_downsample2(ref, ypitch_, ypitch_, mbh_ * 16,
-                                    d_mip1_, ypitch_ / 2, rows_stream_);
-        h264gpu::launch_downsample2(d_mip1_, ypitch_ / 2, ypitch_ / 2,
-                                    mbh_ * 8, ref2, ypitch_ / 4,
+        h264gpu::launch_downsample2(ref, ypitch_, pw, ph, pw, ph, d_mip1_,
+                                    ypitch_ / 2, rows_stream_);
+        h264gpu::launch_downsample2(d_mip1_, ypitch_ / 2, pw / 2, ph / 2,
+                                    pw / 2, ph / 2, ref2, ypitch_ / 4,
                                     rows_stream_);
       }
       h264gpu::launch_h264_me(

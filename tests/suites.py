@@ -45,6 +45,7 @@ _register(Suite(
     "codecs", "Entropy/transform conformance vs the from-spec decoders "
     "(H.264, HEVC, JPEG, Opus)", 0,
     ("test_h264.py", "test_h264_content.py", "test_h264_seg_plan.py",
+     "test_h264_me_mirror_host.py",
      "test_hevc.py", "test_hevc_recon_host.py", "test_jpeg.py",
      "test_opus.py", "test_opus_js.py", "test_rate_control.py",
      "fullcolor/test_h264_fullcolor_host.py",
@@ -78,7 +79,8 @@ _register(Suite(
     ("test_sanitizer.py", "hevc444/test_hevc444_sanitizer.py")))
 _register(Suite(
     "gpu", "Byte-identity + numerics on a real MI355X", 2,
-    ("test_gpu_h264.py", "test_gpu_h264_recon.py", "test_gpu_hevc.py",
+    ("test_gpu_h264.py", "test_gpu_h264_recon.py", "test_gpu_h264_me.py",
+     "test_gpu_hevc.py",
      "test_gpu_hevc_recon.py", "test_gpu_jpeg.py",
      "test_gpu_pipeline_host.py", "test_gpu_tile_comm.py",
      "frontend/test_gpu_frontend.py",
