@@ -292,7 +292,7 @@ __device__ void precompute_mb(const int16_t* levels, const int* meta,
     for (int b = 0; b < 16; ++b) out->ltot[b] = 0;
     for (int b = 0; b < 8; ++b) out->ctot[b] = 0;
   }
-  // chroma mode rides in meta word 1 for intra MBs (see k_h264_rows)
+  // chroma mode rides in meta word 1 for intra MBs (see k_h264_rows4)
   int cmode = (!MONO && mode == kIntra) ? (m1 & 7) : 0;
   out->flags = (short)(mode | (((m0 >> 2) & 7) << 2) | (cmode << 5) |
                        (cbp_luma1 << 8) | (cbp_chroma << 9));

@@ -1,22 +1,54 @@
-// CDNA4 (gfx950) H.264 row kernel, 4-wave variant.
+// CDNA4 (gfx950) H.264 row kernels: transform, quantisation and
+// reconstruction of one slice (an MB row, or a segment of one) per
+// workgroup. Motion search (h264_me.hip) has already chosen every P MB's
+// mode and vector; deblocking and CAVLC follow in their own kernels.
 //
-// The 2-wave kernel's per-MB serial chain is ISSUE-RATE bound: a lone
-// wave on a CDNA SIMD issues one instruction every 4 cycles, so the MB
-// walk's latency is proportional to the per-wave instruction count. This
-// variant splits each MB-row slice across FOUR waves:
-//   wave 0: luma transform passes 0,1 (blocks 0..7)
-//   wave 1: luma transform passes 2,3 (blocks 8..15)
-//   wave 2: chroma Cb (all 4 sub-blocks)
-//   wave 3: chroma Cr
-// Cross-wave state (luma DC coefficients, mode-decision cost halves,
-// left-neighbor recon columns) moves through LDS behind s_barriers — two
-// per intra MB, one per skip/inter MB. The cbp gates on reconstruction
-// are dropped entirely: when cbp is 0 every level is 0 and dequant(0)=0,
-// so gated and ungated recon are bit-identical — this removes the only
-// other cross-wave dependency.
+// The slice's MBs are walked left to right, the one true dependency (H/DC
+// intra prediction reads the left neighbour's reconstruction). That walk
+// is ISSUE-RATE bound: a lone wave on a CDNA SIMD issues one instruction
+// every 4 cycles, so its latency is proportional to the per-wave
+// instruction count. Each MB is therefore spread over the workgroup's
+// waves, 64 lanes = four 4x4 blocks, one lane per coefficient, with the
+// 4x4 transforms done as cross-lane shuffles inside each 16-lane group:
+//   k_h264_rows4 (4:2:0), six waves, 384 threads
+//     waves 0..3: luma, one pass each: wave w codes blocks 4w..4w+3
+//                 (block row w of the MB)
+//     wave 4:     chroma Cb (all four sub-blocks)
+//     wave 5:     chroma Cr
+//   k_h264_rows4_mono (one Hi444 colour plane per slice), four luma
+//     waves, 256 threads, no chroma waves
 //
-// Bit-exactness contract: identical streams to the 2-wave kernel (and so
-// to the CPU reference encoder) — enforced by tests/test_gpu_h264.py.
+// Cross-wave state moves through LDS (Shared) behind workgroup barriers,
+// and every wave of the workgroup takes the same number per MB:
+//   skip / inter MB: ONE barrier, at the end of the MB. It publishes the
+//     next MB's left-neighbour recon columns (lcol / ccol, double-buffered
+//     by MB parity so that a fast wave's writes cannot overtake a slow
+//     wave's reads of the current columns).
+//   intra MB: THREE barriers, paired luma <-> chroma in this order:
+//     1. luma: after the forward pass, the 16 raw luma DCs are in sh->dc
+//        chroma: each wave's H / DC cost halves are in sh->ccost
+//     2. luma: wave 0 has run the DC Hadamard chain and left the
+//        reconstructed DCs in sh->dc ("DC broadcast")
+//        chroma: both waves have read the summed costs
+//     3. end of MB, as for skip / inter.
+//   mono, inter MB: one more barrier before recon, behind which the four
+//     waves OR their "non-zero level" bits (SharedMono::nz); on a hit the
+//     MB is re-coded as intra and takes the three intra barriers as well.
+// Reconstruction is not gated on cbp: when cbp is 0 every level is 0 and
+// dequant(0) = 0, so gated and ungated recon are bit-identical, and no
+// wave has to wait for another's cbp.
+//
+// Contract, and the tests that hold each part:
+//   * IDR streams are byte-identical to the CPU encoder's
+//     (cpu/h264/encoder.cpp): tests/test_gpu_h264.py,
+//     test_gpu_idr_bitstream_matches_cpu_exactly.
+//   * reconstruction equals the from-spec decoder's output for the
+//     kernel's own stream, every plane, padding included:
+//     tests/test_gpu_h264_recon.py; mono:
+//     tests/fullcolor/test_gpu_h264_fullcolor.py.
+//   * P streams (inter dead zone, the 12-coefficient cap) equal the
+//     recorded streams of tests/golden/h264_p_streams.json:
+//     tests/test_gpu_h264_recon.py, test_gpu_p_streams_match_fixture.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -46,6 +78,12 @@ struct SharedMono : Shared {
 };
 
 // ---- luma: wave w handles NP consecutive passes starting at w*NP ---------
+// Both kernels instantiate NP = 1 (four luma waves, wave w = pass w = blocks
+// 4w..4w+3). The parameter and its single-trip loops stay because folding
+// them is not neutral to the compiler: without the loops it reassociates the
+// block index arithmetic and both kernels' code changes (some 30 of 1750
+// instructions fewer, registers reallocated throughout), which wants a
+// measurement of its own.
 // MONO: the slice is a monochrome picture. A monochrome P macroblock can
 // only signal coded_block_pattern 0 here (cpu/h264/encoder.cpp,
 // encode_p16 returning false), so an inter MB whose quantised residual is
@@ -87,8 +125,8 @@ __device__ void luma_wave(const uint8_t* __restrict__ srcY, int ypitch,
     }
 
     if (mode == kSkip) {
-      // both waves cover all 16 rows: wave w copies rows where r parity
-      // is irrelevant — split by halves: wave 0 rows 0..7, wave 1 8..15
+      // the luma waves cover all 16 rows between them: wave w copies rows
+      // 4*NP*w .. 4*NP*(w+1)-1
       if (lane < 16 * NP) {
         int rr = w * 4 * NP + (lane >> 2);   // wave covers 4*NP rows
         int qq = (lane & 3) * 4;

@@ -1,4 +1,5 @@
-// Shared device helpers for the H.264 row kernels (both TUs).
+// Shared device helpers for the H.264 row kernels (h264_rows4.hip) and the
+// motion search (h264_me.hip), the two translation units that include this.
 // __constant__ tables are `static` so each TU gets its own copy (no RDC).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -261,12 +262,6 @@ __device__ inline int wave_sum_i(int v) {
   for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d);
   return v;
 }
-
-__device__ inline int wave_min_i(int v) {
-  for (int d = 1; d < 64; d <<= 1) v = min(v, __shfl_xor(v, d));
-  return v;
-}
-
 
 }  // namespace h264gpu
 }  // namespace hipflux

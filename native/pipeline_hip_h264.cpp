@@ -13,8 +13,7 @@
 // levels/meta hold the planes back to back. Jobs run stripe -> plane ->
 // row -> segment, so one launch each of rows, deblock and CAVLC covers all
 // three planes and each stripe's slices come out plane-major. Motion
-// search runs per plane with that plane's pyramids. HIPFLUX_ROWS_V1 is
-// ignored in this mode: the 2-wave row kernel has no monochrome form.
+// search runs per plane with that plane's pyramids.
 #include <cstdio>
 #include <cstdlib>
 
@@ -206,14 +205,12 @@ class HipH264Pipeline : public EncodePipeline {
     // (all rows run concurrently), so splitting into sequential batches
     // multiplies GPU time (measured: 4 batches regressed 278->155 fps).
     // Entropy overlap is cross-FRAME instead (depth-2 pipelining).
-    // 4-wave row kernel by default (issue-rate-bound chain split across
-    // waves); HIPFLUX_ROWS_V1=1 falls back to the 2-wave variant
     if (fc_)
       h264gpu::launch_h264_rows4_mono(
           d_srcY_, d_refY_, d_curY_, plane_stride_, ypitch_, w_, h_, mbw_,
           n_jobs, d_jobs_[par], d_levels_[par], d_meta_[par], rows_stream_);
     else
-      (rows_v1_ ? h264gpu::launch_h264_rows : h264gpu::launch_h264_rows4)(
+      h264gpu::launch_h264_rows4(
           d_srcY_, d_srcCb_, d_srcCr_, ypitch_, cpitch_, w_, h_, d_refY_,
           d_refCb_, d_refCr_, d_curY_, d_curCb_, d_curCr_, mbw_, n_jobs,
           d_jobs_[par], d_levels_[par], d_meta_[par], rows_stream_);
@@ -698,7 +695,6 @@ class HipH264Pipeline : public EncodePipeline {
          tm_asm_ = 0, tm_concat_ = 0;
   int tm_n_ = 0;
   int ent_stride_words_ = 0;
-  const bool rows_v1_ = std::getenv("HIPFLUX_ROWS_V1") != nullptr;
   std::vector<StripeState> stripes_;
 };
 

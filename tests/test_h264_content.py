@@ -4,7 +4,12 @@ the per-frame stripe mask of the _pipeline_encode test hook. No GPU.
 The GPU reconstruction tests rely on mixed_frames() reaching every MB
 mode and every deblocking strength inside P slices; this file asserts
 that on the CPU pipeline (which shares the mode-decision rules), so the
-generator's coverage cannot rot unseen."""
+generator's coverage cannot rot unseen. It also checks the shape of the
+recorded P-stream fixture those tests compare against."""
+
+import json
+import os
+import re
 
 import numpy as np
 import pytest
@@ -108,6 +113,30 @@ def test_encode_mask_gates_stripes():
     for a, b, c in zip(full, ones, plain):
         key = lambda fr: sorted((y, bytes(d)) for d, y, _, _ in fr)
         assert key(a) == key(b) == key(c)
+
+
+def test_p_stream_fixture_shape():
+    """tests/golden/h264_p_streams.json, which pins the GPU row kernel's
+    P streams (test_gpu_p_streams_match_fixture): the four cases, four
+    frames each, the stripes 0 and 48, a SHA-256 and a length per stream."""
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                        "golden", "h264_p_streams.json")
+    with open(path) as f:
+        doc = json.load(f)
+    n = 4
+    assert doc["content"] == "mixed_frames" and doc["frames"] == n
+    assert doc["stripe_height"] == 48 and doc["pipeline_depth"] == 1
+    note = doc["recorded_from"]
+    assert "2-wave kernel" in note and "mixed_frames" in note
+    assert sorted((c["w"], c["h"], c["qp"]) for c in doc["cases"]) == \
+        [(250, 90, 24), (250, 90, 38), (256, 96, 24), (256, 96, 38)]
+    for c in doc["cases"]:
+        assert len(c["streams"]) == n
+        for frame in c["streams"]:
+            assert sorted(frame) == ["0", "48"]
+            for rec in frame.values():
+                assert re.fullmatch(r"[0-9a-f]{64}", rec["sha256"])
+                assert isinstance(rec["length"], int) and rec["length"] > 0
 
 
 @pytest.mark.parametrize("bad", [
