@@ -160,31 +160,16 @@ class CabacEncoder {
   int num_buffered_ = 0;
 };
 
-// Full I-slice context bank, initialized per §9.3.2.2 (initType 0).
+// Full context bank, initialized per §9.3.2.2. init_type 0 = I slice,
+// 1 = P slice (cabac_init_flag 0); the P-only contexts sit past
+// kNumContexts and are never touched by I-slice syntax.
 struct ContextBank {
-  Ctx ctx[kNumContexts];
+  Ctx ctx[kNumContextsP];
 
-  void init(int qp) {
-    for (int i = 0; i < 3; ++i)
-      ctx[kCtxSplitCu + i].init(kInitSplitCuFlag[i], qp);
-    ctx[kCtxPrevIntraLuma].init(kInitPrevIntraLumaPredFlag, qp);
-    ctx[kCtxIntraChroma].init(kInitIntraChromaPredMode, qp);
-    for (int i = 0; i < 2; ++i)
-      ctx[kCtxCbfLuma + i].init(kInitCbfLuma[i], qp);
-    for (int i = 0; i < 4; ++i)
-      ctx[kCtxCbfChroma + i].init(kInitCbfChroma[i], qp);
-    for (int i = 0; i < 18; ++i) {
-      ctx[kCtxLastSigX + i].init(kInitLastSigXPrefix[i], qp);
-      ctx[kCtxLastSigY + i].init(kInitLastSigYPrefix[i], qp);
-    }
-    for (int i = 0; i < 4; ++i)
-      ctx[kCtxCodedSubBlock + i].init(kInitCodedSubBlockFlag[i], qp);
-    for (int i = 0; i < 42; ++i)
-      ctx[kCtxSigCoeff + i].init(kInitSigCoeffFlag[i], qp);
-    for (int i = 0; i < 24; ++i)
-      ctx[kCtxGreater1 + i].init(kInitGreater1Flag[i], qp);
-    for (int i = 0; i < 6; ++i)
-      ctx[kCtxGreater2 + i].init(kInitGreater2Flag[i], qp);
+  void init(int qp, int init_type = 0) {
+    uint8_t iv[kNumContextsP];
+    fill_init_values(init_type, iv);
+    for (int i = 0; i < kNumContextsP; ++i) ctx[i].init(iv[i], qp);
   }
 };
 

@@ -46,11 +46,15 @@ struct StripeEncoder::Impl {
   std::vector<uint8_t> luma_mode;           // per-CTU chosen mode
   std::vector<uint8_t> ps_cache;            // VPS/SPS/PPS bytes
   int ypitch, cpitch;
+  bool inter;          // P pictures enabled (4:2:0 only)
+  bool have_ref = false;   // recon planes hold the previous coded picture
+  int poc = 0;             // POC of the next picture (0 after an IDR)
 
-  Impl(int width, int height, int spr, bool fc)
+  Impl(int width, int height, int spr, bool fc, bool inter_on)
       : w(width), h(height), cw((width + 15) & ~15), ch((height + 15) & ~15),
         ctb_w(cw / 16), ctb_h(ch / 16),
-        slices_per_row(std::max(1, std::min(spr, cw / 16))), fullcolor(fc) {
+        slices_per_row(std::max(1, std::min(spr, cw / 16))), fullcolor(fc),
+        inter(inter_on && !fc) {
     int n_ctb = ctb_w * ctb_h;
     addr_bits = 1;
     while ((1 << addr_bits) < n_ctb) ++addr_bits;
@@ -64,8 +68,8 @@ struct StripeEncoder::Impl {
     scb = rcb;
     scr = rcr;
     luma_mode.resize(n_ctb);
-    write_vps_nal(ps_cache, level_idc_for(cw, ch), fullcolor);
-    write_sps_nal(ps_cache, cw, ch, w, h, fullcolor);
+    write_vps_nal(ps_cache, level_idc_for(cw, ch), fullcolor, inter);
+    write_sps_nal(ps_cache, cw, ch, w, h, fullcolor, inter);
     write_pps_nal(ps_cache);
   }
 
@@ -101,8 +105,14 @@ struct StripeEncoder::Impl {
 
   // Encode one 16x16 CTU: choose mode, transform, reconstruct, and emit
   // CABAC bins. left_avail reflects the slice-segment boundary.
+  // In a P slice (p_slice) the zero-motion merge candidate competes: the
+  // predictor of every sample is the sample it overwrites in the recon
+  // planes (the previous coded picture), so recon updates in place.
+  // left_mode is the left CTU's luma_mode[] entry (intra mode, or a
+  // CtuKind for inter CTUs).
   void encode_ctu(CabacEncoder& cab, ContextBank& bank, int cx, int cy,
-                  bool left_avail, int qp, uint8_t left_mode) {
+                  bool left_avail, int qp, uint8_t left_mode,
+                  bool p_slice = false) {
     const int x0 = cx * 16, y0 = cy * 16;
     // --- luma mode decision + transform
     Avail av;  // one slice per CTU row: only left neighbors exist
@@ -115,7 +125,7 @@ struct StripeEncoder::Impl {
     filter_refs<16>(ref, reff);
 
     static const int kModes[4] = {kDc, kHor, kVer, kPlanar};
-    uint8_t pred[4][256];
+    uint8_t pred[5][256];   // 4 intra candidates + the inter reference
     int best = 0;
     long best_sad = LONG_MAX;
     for (int m = 0; m < 4; ++m) {
@@ -135,6 +145,23 @@ struct StripeEncoder::Impl {
     const int mode = kModes[best];
     luma_mode[cy * ctb_w + cx] = static_cast<uint8_t>(mode);
 
+    bool is_inter = false;
+    if (p_slice) {
+      // reference reads are the coded-size recon plane, unclamped
+      long sad_inter = 0;
+      for (int yy = 0; yy < 16; ++yy)
+        for (int xx = 0; xx < 16; ++xx) {
+          const size_t o = static_cast<size_t>(y0 + yy) * ypitch + x0 + xx;
+          int d = sy[o] - ry[o];
+          sad_inter += d < 0 ? -d : d;
+          pred[4][yy * 16 + xx] = ry[o];
+        }
+      is_inter = sad_inter <= best_sad;
+      if (is_inter) best = 4;
+    }
+    // HM rounding: 171/512 intra, 85/512 inter, in all three planes
+    const int round = is_inter ? 85 : 171;
+
     int16_t res[256], coef[256];
     TbData<16> yb;
     for (int yy = 0; yy < 16; ++yy)
@@ -144,7 +171,7 @@ struct StripeEncoder::Impl {
                 sy[static_cast<size_t>(y0 + yy) * ypitch + x0 + xx] -
                 pred[best][yy * 16 + xx]);
     fwd_transform<16>(res, 16, coef);
-    yb.cbf = quantize<16>(coef, qp, yb.level) != 0;
+    yb.cbf = quantize<16>(coef, qp, yb.level, round) != 0;
     if (yb.cbf) {
       int16_t deq[256], rres[256];
       dequantize<16>(yb.level, qp, deq);
@@ -175,8 +202,14 @@ struct StripeEncoder::Impl {
       const uint8_t* sp = pl ? scr.data() : scb.data();
       TbData<8>& tb = pl ? crb : cbb;
       uint8_t cref[33];
-      build_refs<8>(rp, cpitch, cx0, cy0, av, cref);
-      predict<8>(mode, cref, 1, cpred[pl]);
+      if (is_inter) {
+        for (int yy = 0; yy < 8; ++yy)
+          std::memcpy(&cpred[pl][yy * 8],
+                      &rp[static_cast<size_t>(cy0 + yy) * cpitch + cx0], 8);
+      } else {
+        build_refs<8>(rp, cpitch, cx0, cy0, av, cref);
+        predict<8>(mode, cref, 1, cpred[pl]);
+      }
       int16_t cres[64], ccoef[64];
       for (int yy = 0; yy < 8; ++yy)
         for (int xx = 0; xx < 8; ++xx)
@@ -184,7 +217,7 @@ struct StripeEncoder::Impl {
               sp[static_cast<size_t>(cy0 + yy) * cpitch + cx0 + xx] -
               cpred[pl][yy * 8 + xx]);
       fwd_transform<8>(cres, 8, ccoef);
-      tb.cbf = quantize<8>(ccoef, qpc, tb.level) != 0;
+      tb.cbf = quantize<8>(ccoef, qpc, tb.level, round) != 0;
       if (tb.cbf) {
         int16_t deq[64], rres[64];
         dequantize<8>(tb.level, qpc, deq);
@@ -201,8 +234,20 @@ struct StripeEncoder::Impl {
     }
 
     // --- CABAC bins for the CTU (shared emission path, entropy.h)
-    code_ctu_syntax(cab, bank, mode, left_avail ? left_mode : -1, yb.cbf,
-                    cbb.cbf, crb.cbf, yb.level, cbb.level, crb.level);
+    if (!p_slice) {
+      code_ctu_syntax(cab, bank, mode, left_avail ? left_mode : -1, yb.cbf,
+                      cbb.cbf, crb.cbf, yb.level, cbb.level, crb.level);
+      return;
+    }
+    // inter with no coded residual is a skip (recon == reference already)
+    const int kind = !is_inter                          ? kCtuIntra
+                     : (yb.cbf || cbb.cbf || crb.cbf) ? kCtuMerge
+                                                      : kCtuSkip;
+    if (is_inter) luma_mode[cy * ctb_w + cx] = static_cast<uint8_t>(kind);
+    code_ctu_syntax_p(cab, bank, kind, left_avail && left_mode == kCtuSkip,
+                      mode, left_avail && left_mode < 35 ? left_mode : -1,
+                      yb.cbf, cbb.cbf, crb.cbf, yb.level, cbb.level,
+                      crb.level);
   }
 
   // 4:4:4 chroma (DM mode): Cb and Cr are 16x16 TBs coded like luma with
@@ -256,8 +301,8 @@ struct StripeEncoder::Impl {
 };
 
 StripeEncoder::StripeEncoder(int width, int height, int slices_per_row,
-                             bool fullcolor)
-    : impl_(new Impl(width, height, slices_per_row, fullcolor)),
+                             bool fullcolor, bool inter)
+    : impl_(new Impl(width, height, slices_per_row, fullcolor, inter)),
       width_(width),
       height_(height) {}
 
@@ -273,11 +318,17 @@ void StripeEncoder::encode_frame(const uint8_t* y, int ypitch,
                                  const uint8_t* cb, const uint8_t* cr,
                                  int cpitch, int qp,
                                  std::vector<uint8_t>& out,
-                                 EncodeStats* stats) {
+                                 EncodeStats* stats, bool force_idr) {
   Impl& im = *impl_;
   qp = std::clamp(qp, 0, 51);
   im.load_source(y, ypitch, cb, cr, cpitch);
-  out.insert(out.end(), im.ps_cache.begin(), im.ps_cache.end());
+  const bool p_slice = im.inter && im.have_ref && !force_idr;
+  if (!p_slice) {
+    // IDR: POC 0, parameter sets in front. P emissions carry none.
+    im.poc = 0;
+    out.insert(out.end(), im.ps_cache.begin(), im.ps_cache.end());
+  }
+  const int poc_lsb = im.poc & 255;
 
   // one slice segment per CTU row (split into slices_per_row segments)
   for (int cy = 0; cy < im.ctb_h; ++cy) {
@@ -286,14 +337,18 @@ void StripeEncoder::encode_frame(const uint8_t* y, int ypitch,
       int s1 = std::min(s0 + per, im.ctb_w);
       BitWriter bw;
       bool first = (cy == 0 && s0 == 0);
-      write_slice_header(bw, first, cy * im.ctb_w + s0, im.addr_bits, qp);
+      if (p_slice)
+        write_p_slice_header(bw, first, cy * im.ctb_w + s0, im.addr_bits, qp,
+                             poc_lsb);
+      else
+        write_slice_header(bw, first, cy * im.ctb_w + s0, im.addr_bits, qp);
       std::vector<uint8_t> cabac_bytes;
       CabacEncoder cab(cabac_bytes);
       ContextBank bank;
-      bank.init(qp);
+      bank.init(qp, p_slice ? 1 : 0);
       uint8_t left_mode = kDc;
       for (int cx = s0; cx < s1; ++cx) {
-        im.encode_ctu(cab, bank, cx, cy, cx > s0, qp, left_mode);
+        im.encode_ctu(cab, bank, cx, cy, cx > s0, qp, left_mode, p_slice);
         left_mode = im.luma_mode[cy * im.ctb_w + cx];
         cab.encode_terminate(cx == s1 - 1 ? 1 : 0);
       }
@@ -302,10 +357,14 @@ void StripeEncoder::encode_frame(const uint8_t* y, int ypitch,
       bw.u(tail.bits, tail.nbits);
       // rbsp_slice_segment_trailing_bits: stop bit + alignment
       bw.rbsp_trailing();
-      emit_nal(bw, out, kNalIdr);
+      emit_nal(bw, out, p_slice ? kNalTrailR : kNalIdr);
     }
   }
+  // POC advances per coded picture of this stripe (8 lsb bits on the wire)
+  ++im.poc;
+  im.have_ref = true;
   if (stats) {
+    stats->idr = !p_slice;
     stats->frame_qp = qp;
     stats->ctu_count = im.ctb_w * im.ctb_h;
     stats->bytes = out.size();

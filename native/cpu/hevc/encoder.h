@@ -5,6 +5,12 @@
 // pixelflux has no HEVC):
 //  * Main profile, all-intra (every frame IDR), CABAC, 4:2:0, bit depth 8;
 //    or with `fullcolor` Main 4:4:4 (chroma_format_idc 3).
+//  * Opt-in (`inter`, 4:2:0): I + zero-motion P. A P picture references
+//    the previous coded picture of the stripe; its CTUs are skip, merge +
+//    residual (MV 0, MaxNumMergeCand 1) or intra. Zero motion makes each
+//    sample's predictor the sample it overwrites, so the recon planes
+//    update in place and no second reference plane exists. No motion
+//    search, no mvd/AMVP, no sub-pel interpolation.
 //  * CTU = CU = PU = 16x16, one 16x16 luma TB + two 8x8 chroma TBs (two
 //    16x16 chroma TBs in 4:4:4), no residual quadtree. This keeps the flat per-16px-row geometry the
 //    stripe wire format and the HIP row-wavefront kernels are built
@@ -32,6 +38,7 @@ struct EncodeStats {
   int frame_qp = 0;
   int ctu_count = 0;
   size_t bytes = 0;
+  bool idr = true;   // false: the emission was a P picture
 };
 
 // Slice segments per CTU row, shared by the CPU and HIP pipelines so their
@@ -60,8 +67,11 @@ class StripeEncoder {
   // conformance-window crop). slices_per_row splits each CTU row into
   // independent slice segments for entropy parallelism. fullcolor codes
   // 4:4:4 (Main 4:4:4 profile, chroma TBs 16x16) instead of 4:2:0.
+  // inter (4:2:0 only; ignored with fullcolor) turns every picture after
+  // the first into a P picture of zero-motion merge/skip and intra CTUs
+  // that references the previous coded picture, until force_idr.
   StripeEncoder(int width, int height, int slices_per_row = 1,
-                bool fullcolor = false);
+                bool fullcolor = false, bool inter = false);
   ~StripeEncoder();
 
   // Encode one frame from planar YUV420 (pitch in bytes, planes at least
@@ -71,7 +81,8 @@ class StripeEncoder {
   // are coded-size with recon_cpitch() == recon_ypitch().
   void encode_frame(const uint8_t* y, int ypitch, const uint8_t* cb,
                     const uint8_t* cr, int cpitch, int qp,
-                    std::vector<uint8_t>& out, EncodeStats* stats = nullptr);
+                    std::vector<uint8_t>& out, EncodeStats* stats = nullptr,
+                    bool force_idr = false);
 
   const uint8_t* recon_y() const;
   const uint8_t* recon_cb() const;

@@ -224,17 +224,13 @@ inline void code_residual(CabacEncoder& cab, ContextBank& bank,
   }
 }
 
-// All CABAC bins of one CTU (coding_quadtree -> coding_unit ->
-// transform_tree): split flag, intra mode w/ MPM, chroma DM, cbfs,
-// residuals. left_mode < 0 means the left CTU is unavailable (slice
-// start). Levels are raster [y*N + x] arrays; cbf flags must match
-// their content (cbf set <=> any nonzero).
-inline void code_ctu_syntax(CabacEncoder& cab, ContextBank& bank, int mode,
-                            int left_mode, bool cbf_y, bool cbf_cb,
-                            bool cbf_cr, const int16_t* ylv,
-                            const int16_t* cblv, const int16_t* crlv,
-                            bool fullcolor = false) {
-  cab.encode_bin(bank.ctx[kCtxSplitCu + 0], 0);  // split_cu_flag
+// coding_unit body of an intra 2Nx2N CU from prev_intra_luma_pred_flag on
+// (identical in I and P slices): MPM, chroma DM, cbfs, residuals.
+inline void code_intra_cu_syntax(CabacEncoder& cab, ContextBank& bank,
+                                 int mode, int left_mode, bool cbf_y,
+                                 bool cbf_cb, bool cbf_cr, const int16_t* ylv,
+                                 const int16_t* cblv, const int16_t* crlv,
+                                 bool fullcolor) {
   // MPM derivation (§8.4.2): above PU is outside the CTU row -> DC.
   int cand_a = left_mode >= 0 ? left_mode : kDc;
   int cand_b = kDc;
@@ -293,6 +289,60 @@ inline void code_ctu_syntax(CabacEncoder& cab, ContextBank& bank, int mode,
     if (cbf_cb) code_residual<8>(cab, bank, cblv, 1);
     if (cbf_cr) code_residual<8>(cab, bank, crlv, 2);
   }
+}
+
+// All CABAC bins of one CTU (coding_quadtree -> coding_unit ->
+// transform_tree): split flag, intra mode w/ MPM, chroma DM, cbfs,
+// residuals. left_mode < 0 means the left CTU is unavailable (slice
+// start). Levels are raster [y*N + x] arrays; cbf flags must match
+// their content (cbf set <=> any nonzero).
+inline void code_ctu_syntax(CabacEncoder& cab, ContextBank& bank, int mode,
+                            int left_mode, bool cbf_y, bool cbf_cb,
+                            bool cbf_cr, const int16_t* ylv,
+                            const int16_t* cblv, const int16_t* crlv,
+                            bool fullcolor = false) {
+  cab.encode_bin(bank.ctx[kCtxSplitCu + 0], 0);  // split_cu_flag
+  code_intra_cu_syntax(cab, bank, mode, left_mode, cbf_y, cbf_cb, cbf_cr, ylv,
+                       cblv, crlv, fullcolor);
+}
+
+// CTU kinds of a P slice. The values double as the GPU meta "mode" word
+// for inter CTUs (native/hip/hevc_gpu_layout.h); intra CTUs keep 0..34.
+enum CtuKind { kCtuIntra = 0, kCtuMerge = 64, kCtuSkip = 65 };
+
+// All CABAC bins of one CTU of a P slice (4:2:0 only). left_skip: the left
+// CTU is in this slice segment and is a skip CU (cu_skip_flag ctxInc; the
+// above CTU is in another slice). left_mode: the left CTU's intra mode, or
+// < 0 when it is absent or not intra (MPM candidate A = DC, §8.4.2).
+// Merge CUs are 2Nx2N with MaxNumMergeCand 1: no merge_idx, and
+// rqt_root_cbf is not coded (inferred 1), so a merge CU must have a cbf
+// set; cbf_luma is coded only when a chroma cbf is set (else inferred 1).
+inline void code_ctu_syntax_p(CabacEncoder& cab, ContextBank& bank, int kind,
+                              bool left_skip, int mode, int left_mode,
+                              bool cbf_y, bool cbf_cb, bool cbf_cr,
+                              const int16_t* ylv, const int16_t* cblv,
+                              const int16_t* crlv) {
+  cab.encode_bin(bank.ctx[kCtxSplitCu + 0], 0);  // split_cu_flag
+  cab.encode_bin(bank.ctx[kCtxCuSkip + (left_skip ? 1 : 0)],
+                 kind == kCtuSkip ? 1 : 0);      // cu_skip_flag
+  if (kind == kCtuSkip) return;                  // merge_idx not coded
+  cab.encode_bin(bank.ctx[kCtxPredMode], kind == kCtuIntra ? 1 : 0);
+  if (kind == kCtuIntra) {
+    // no part_mode: log2CbSize 4 != MinCbLog2SizeY 3
+    code_intra_cu_syntax(cab, bank, mode, left_mode, cbf_y, cbf_cb, cbf_cr,
+                         ylv, cblv, crlv, false);
+    return;
+  }
+  cab.encode_bin(bank.ctx[kCtxPartMode], 1);     // part_mode: 2Nx2N
+  cab.encode_bin(bank.ctx[kCtxMergeFlag], 1);    // merge_flag
+  // transform_tree at depth 0, no split flag (max inter depth 0)
+  cab.encode_bin(bank.ctx[kCtxCbfChroma + 0], cbf_cb ? 1 : 0);
+  cab.encode_bin(bank.ctx[kCtxCbfChroma + 0], cbf_cr ? 1 : 0);
+  if (cbf_cb || cbf_cr)
+    cab.encode_bin(bank.ctx[kCtxCbfLuma + 1], cbf_y ? 1 : 0);
+  if (cbf_y) code_residual<16>(cab, bank, ylv, 0);
+  if (cbf_cb) code_residual<8>(cab, bank, cblv, 1);
+  if (cbf_cr) code_residual<8>(cab, bank, crlv, 2);
 }
 
 }  // namespace hevc

@@ -9,7 +9,7 @@ namespace hevc {
 
 using h264::BitWriter;
 
-enum NalType { kNalIdr = 19, kNalVps = 32, kNalSps = 33, kNalPps = 34 };
+enum NalType { kNalTrailR = 1, kNalIdr = 19, kNalVps = 32, kNalSps = 33, kNalPps = 34 };
 
 // Append one HEVC NAL (2-byte header, §7.3.1.2) with start code and
 // emulation prevention.
@@ -77,8 +77,10 @@ inline void write_ptl(BitWriter& b, int level_idc, bool fullcolor = false) {
   b.u(level_idc, 8);
 }
 
+// inter: the stream holds P pictures with one reference, so the decoded
+// picture buffer is two pictures deep (VPS and SPS alike).
 inline void write_vps_nal(std::vector<uint8_t>& out, int level_idc,
-                          bool fullcolor = false) {
+                          bool fullcolor = false, bool inter = false) {
   BitWriter b;
   b.u(0, 4);   // vps_video_parameter_set_id
   b.u(1, 1);   // vps_base_layer_internal_flag
@@ -89,7 +91,7 @@ inline void write_vps_nal(std::vector<uint8_t>& out, int level_idc,
   b.u(0xFFFF, 16);  // vps_reserved_0xffff_16bits
   write_ptl(b, level_idc, fullcolor);
   b.u(1, 1);   // vps_sub_layer_ordering_info_present (code layer 0)
-  b.ue(0);     // vps_max_dec_pic_buffering_minus1
+  b.ue(inter ? 1 : 0);  // vps_max_dec_pic_buffering_minus1
   b.ue(0);     // vps_max_num_reorder_pics
   b.ue(0);     // vps_max_latency_increase_plus1
   b.u(0, 6);   // vps_max_layer_id
@@ -105,7 +107,8 @@ inline void write_vps_nal(std::vector<uint8_t>& out, int level_idc,
 // the window offsets are then in units of SubWidthC = SubHeightC = 1, so
 // odd visible sizes crop exactly. No SPS range extension is needed.
 inline void write_sps_nal(std::vector<uint8_t>& out, int coded_w, int coded_h,
-                          int width, int height, bool fullcolor = false) {
+                          int width, int height, bool fullcolor = false,
+                          bool inter = false) {
   BitWriter b;
   b.u(0, 4);   // sps_video_parameter_set_id
   b.u(0, 3);   // sps_max_sub_layers_minus1
@@ -135,7 +138,7 @@ inline void write_sps_nal(std::vector<uint8_t>& out, int coded_w, int coded_h,
   b.ue(0);     // bit_depth_chroma_minus8
   b.ue(4);     // log2_max_pic_order_cnt_lsb_minus4
   b.u(1, 1);   // sps_sub_layer_ordering_info_present_flag
-  b.ue(0);     // sps_max_dec_pic_buffering_minus1
+  b.ue(inter ? 1 : 0);  // sps_max_dec_pic_buffering_minus1
   b.ue(0);     // sps_max_num_reorder_pics
   b.ue(0);     // sps_max_latency_increase_plus1
   b.ue(0);     // log2_min_luma_coding_block_size_minus3 (8)
@@ -148,7 +151,17 @@ inline void write_sps_nal(std::vector<uint8_t>& out, int coded_w, int coded_h,
   b.u(0, 1);   // amp_enabled_flag
   b.u(0, 1);   // sample_adaptive_offset_enabled_flag
   b.u(0, 1);   // pcm_enabled_flag
-  b.ue(0);     // num_short_term_ref_pic_sets
+  if (inter) {
+    // one candidate RPS: the previous picture in decoding order
+    b.ue(1);     // num_short_term_ref_pic_sets
+    // st_ref_pic_set(0): idx 0 has no inter_ref_pic_set_prediction_flag
+    b.ue(1);     // num_negative_pics
+    b.ue(0);     // num_positive_pics
+    b.ue(0);     // delta_poc_s0_minus1[0]
+    b.u(1, 1);   // used_by_curr_pic_s0_flag[0]
+  } else {
+    b.ue(0);     // num_short_term_ref_pic_sets
+  }
   b.u(0, 1);   // long_term_ref_pics_present_flag
   b.u(0, 1);   // sps_temporal_mvp_enabled_flag
   b.u(0, 1);   // strong_intra_smoothing_enabled_flag
@@ -207,6 +220,32 @@ inline void write_slice_header(BitWriter& b, bool first_slice,
   // deblocking: pps disabled + no override -> nothing to code
   // byte_alignment()
   b.put_bit(1);
+  while (b.bit_count() % 8) b.put_bit(0);
+}
+
+// P (TRAIL_R) slice segment header; returns byte-aligned like the above.
+// Re-derived from §7.3.6.1 against this encoder's SPS/PPS, every other
+// field is absent: not IRAP (no no_output_of_prior_pics_flag), no
+// dependent slices, no extra header bits, no output flag, one colour
+// plane group; one SPS RPS (short_term_ref_pic_set_idx is u(0)), no
+// long-term pictures, no temporal MVP, no SAO; lists_modification off and
+// a P slice has no mvd_l1_zero_flag; cabac_init_present_flag 0; no
+// weighted prediction; no slice chroma offsets, no deblocking override
+// and pps_loop_filter_across_slices off (so no slice flag); no tiles or
+// wavefronts (no entry points); no header extension.
+inline void write_p_slice_header(BitWriter& b, bool first_slice,
+                                 int slice_address, int addr_bits, int qp,
+                                 int poc_lsb) {
+  b.u(first_slice ? 1 : 0, 1);  // first_slice_segment_in_pic_flag
+  b.ue(0);                      // slice_pic_parameter_set_id
+  if (!first_slice) b.u(slice_address, addr_bits);
+  b.ue(1);                      // slice_type: P
+  b.u(poc_lsb & 255, 8);        // slice_pic_order_cnt_lsb (8 lsb bits)
+  b.u(1, 1);                    // short_term_ref_pic_set_sps_flag
+  b.u(0, 1);                    // num_ref_idx_active_override_flag
+  b.ue(4);                      // five_minus_max_num_merge_cand (1 cand)
+  b.se(qp - 26);                // slice_qp_delta
+  b.put_bit(1);                 // byte_alignment()
   while (b.bit_count() % 8) b.put_bit(0);
 }
 

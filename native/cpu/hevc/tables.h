@@ -1,7 +1,7 @@
 // HEVC (ITU-T H.265) constant tables — transcribed from the spec for the
-// subset this encoder emits (all-intra, CTU16, TB16 luma / TB8 chroma,
-// CABAC). Single source of truth: the GPU entropy stage includes this
-// header too. Table numbers cite the 2013-04 H.265 text.
+// subset this encoder emits (I pictures, opt-in zero-motion P pictures,
+// CTU16, TB16 luma / TB8 chroma, CABAC). Single source of truth: the GPU
+// entropy stage includes this header too. Table numbers cite the 2013-04 H.265 text.
 //
 // The reference project carries no HEVC encoder (pixelflux is
 // H.264/JPEG only; HEVC is a BASELINE.json config-3 target for this
@@ -94,7 +94,68 @@ enum CtxOffset {
   kCtxGreater1 = 93,               // 24
   kCtxGreater2 = 117,              // 6
   kNumContexts = 123,
+  // P-slice-only contexts, appended so the I-slice offsets do not move
+  kCtxCuSkip = 123,                // 3
+  kCtxPredMode = 126,              // 1
+  kCtxPartMode = 127,              // 1 (bin 0 only: 2Nx2N)
+  kCtxMergeFlag = 128,             // 1
+  kNumContextsP = 129,
 };
+
+// ---- Context initValues, initType 1 (P slices, cabac_init_flag 0) --------
+// Tables 9-5..9-37, second column group. Same layout as the initType-0
+// arrays; the cross-check of this transcription is in profiles/NOTES.md.
+inline const uint8_t kInit1SplitCuFlag[3] = {107, 139, 126};
+inline const uint8_t kInit1CuSkipFlag[3] = {197, 185, 201};
+inline const uint8_t kInit1PredModeFlag = 149;
+inline const uint8_t kInit1PartMode0 = 154;
+inline const uint8_t kInit1MergeFlag = 110;
+inline const uint8_t kInit1PrevIntraLumaPredFlag = 154;
+inline const uint8_t kInit1IntraChromaPredMode = 152;
+inline const uint8_t kInit1CbfLuma[2] = {153, 111};
+inline const uint8_t kInit1CbfChroma[4] = {149, 107, 167, 154};
+inline const uint8_t kInit1LastSigXPrefix[18] = {
+    125, 110, 94,  110, 95,  79,  125, 111, 110,
+    78,  110, 111, 111, 95,  94,  108, 123, 108};
+inline const uint8_t kInit1LastSigYPrefix[18] = {
+    125, 110, 94,  110, 95,  79,  125, 111, 110,
+    78,  110, 111, 111, 95,  94,  108, 123, 108};
+inline const uint8_t kInit1CodedSubBlockFlag[4] = {121, 140, 61, 154};
+inline const uint8_t kInit1SigCoeffFlag[42] = {
+    155, 154, 139, 153, 139, 123, 123, 63,  153, 166, 183, 140, 136, 153,
+    154, 166, 183, 140, 136, 153, 154, 166, 183, 140, 136, 153, 154, 170,
+    153, 123, 123, 107, 121, 107, 121, 167, 151, 183, 140, 151, 183, 140};
+inline const uint8_t kInit1Greater1Flag[24] = {
+    154, 196, 196, 167, 154, 152, 167, 182, 182, 134, 149, 136,
+    153, 121, 136, 137, 169, 194, 166, 167, 154, 167, 137, 182};
+inline const uint8_t kInit1Greater2Flag[6] = {107, 167, 91, 122, 107, 167};
+
+// All initValues of one initType in context-bank order (CtxOffset). The
+// six P-only entries of initType 0 do not exist in the spec (an I slice
+// never codes them) and are filled with 154 (equiprobable).
+inline void fill_init_values(int init_type, uint8_t out[129]) {
+  const bool p = init_type == 1;
+  int n = 0;
+  auto put = [&](const uint8_t* a0, const uint8_t* a1, int cnt) {
+    for (int i = 0; i < cnt; ++i) out[n++] = p ? a1[i] : a0[i];
+  };
+  const uint8_t cnu[3] = {154, 154, 154};
+  put(kInitSplitCuFlag, kInit1SplitCuFlag, 3);
+  put(&kInitPrevIntraLumaPredFlag, &kInit1PrevIntraLumaPredFlag, 1);
+  put(&kInitIntraChromaPredMode, &kInit1IntraChromaPredMode, 1);
+  put(kInitCbfLuma, kInit1CbfLuma, 2);
+  put(kInitCbfChroma, kInit1CbfChroma, 4);
+  put(kInitLastSigXPrefix, kInit1LastSigXPrefix, 18);
+  put(kInitLastSigYPrefix, kInit1LastSigYPrefix, 18);
+  put(kInitCodedSubBlockFlag, kInit1CodedSubBlockFlag, 4);
+  put(kInitSigCoeffFlag, kInit1SigCoeffFlag, 42);
+  put(kInitGreater1Flag, kInit1Greater1Flag, 24);
+  put(kInitGreater2Flag, kInit1Greater2Flag, 6);
+  put(cnu, kInit1CuSkipFlag, 3);
+  put(cnu, &kInit1PredModeFlag, 1);
+  put(cnu, &kInit1PartMode0, 1);
+  put(cnu, &kInit1MergeFlag, 1);
+}
 
 // ---- Scan (§6.5.3 up-right diagonal) -------------------------------------
 // Positions in coding order for a 4x4 block: kDiagScan4[i] = (x, y).

@@ -60,13 +60,15 @@ inline void inv_transform(const int16_t* coef, int16_t* res, int res_stride) {
     }
 }
 
-// Quantization (HM rounding, intra offset 171/512).
+// Quantization (HM rounding: offset 171/512 for intra blocks, 85/512 for
+// inter blocks).
 template <int N>
-inline int quantize(const int16_t* coef, int qp, int16_t* level) {
+inline int quantize(const int16_t* coef, int qp, int16_t* level,
+                    int round = 171) {
   const int log2n = N == 8 ? 3 : 4;
   const int qbits = 14 + qp / 6 + (15 - 8 - log2n);
   const int scale = kQuantScale[qp % 6];
-  const int add = 171 << (qbits - 9);
+  const int add = round << (qbits - 9);
   int nz = 0;
   for (int i = 0; i < N * N; ++i) {
     int c = coef[i];

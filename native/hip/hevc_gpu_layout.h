@@ -10,7 +10,9 @@
 //     +256  .. 511 : Cb 16x16
 //     +512  .. 767 : Cr 16x16
 //   meta[(ctu_row * ctbw + ctu_x) * kHevcMetaPerCtu]
-//     +0 : chosen intra mode (0 planar / 1 dc / 10 hor / 26 ver)
+//     +0 : chosen intra mode (0 planar / 1 dc / 10 hor / 26 ver); in a P
+//          slice also kHevcMetaMerge (zero-motion merge + residual) or
+//          kHevcMetaSkip (skip), values outside the intra range 0..34
 //     +1 : cbf mask (bit0 luma, bit1 cb, bit2 cr)
 #pragma once
 
@@ -22,6 +24,8 @@ namespace hevcgpu {
 constexpr int kHevcLevelsPerCtu = 384;
 constexpr int kHevcLevelsPerCtu444 = 768;
 constexpr int kHevcMetaPerCtu = 2;
+constexpr int kHevcMetaMerge = 64;   // == hevc::kCtuMerge
+constexpr int kHevcMetaSkip = 65;    // == hevc::kCtuSkip
 
 // One slice-segment job (one CABAC stream; one row-kernel workgroup).
 struct HevcJob {
@@ -35,6 +39,9 @@ struct HevcJob {
   int slice_addr;   // CTU address within the stripe picture
   int addr_bits;    // bits of slice_segment_address in this stripe
   int last_in_pic;  // 1 = this segment codes end_of_slice = 1 at its end
+  int slice_type;   // 2 = I (IDR), 1 = P (zero-motion merge/skip + intra);
+                    // only the *_p kernels read it
+  int poc_lsb;      // slice_pic_order_cnt_lsb of a P slice (host header)
 };
 
 }  // namespace hevcgpu

@@ -10,6 +10,10 @@
 //    8x8 planes run on threads 0..63 / 64..127 concurrently.
 //  * k_hevc_rows444: the 4:4:4 (fullcolor) form; three 16x16 planes side
 //    by side on a 768-thread workgroup (see its own header).
+//  * k_hevc_rows_p / k_hevc_cabac_p: siblings of the 4:2:0 kernels for
+//    frames that hold P jobs (hevc_inter): zero-motion merge / skip CTUs
+//    predicted from the recon planes in place, plus intra (see their own
+//    headers). The I kernels are not touched by them.
 //  * k_hevc_cabac: CABAC is bin-serial per slice, so one LANE encodes one
 //    slice segment; parallelism comes from the many independent segments
 //    (4K: 135 rows x slices/row). The bin semantics transliterate
@@ -94,6 +98,9 @@ struct RowsShared {
 
 __device__ const int kModeOrder[4] = {1, 10, 26, 0};  // DC, H, V, Planar
 
+// Sibling: k_hevc_rows_p below repeats this kernel's intra path line for
+// line (it exists apart so that this kernel's code stays as it is). A fix
+// here has to be made there too.
 __global__ __launch_bounds__(256) void k_hevc_rows(
     const uint8_t* __restrict__ srcY, const uint8_t* __restrict__ srcCb,
     const uint8_t* __restrict__ srcCr, int ypitch, int cpitch, int w, int h,
@@ -374,6 +381,344 @@ __global__ __launch_bounds__(256) void k_hevc_rows(
   }
 }
 
+// ---- rows kernel, P pictures ---------------------------------------------
+// Sibling of k_hevc_rows for frames that hold P jobs (the I kernel stays
+// as it is; with no P job in a frame it is the one launched). Per CTU of a
+// P job it adds the co-located reference load, a fifth SAD, the
+// inter/intra select and the inter rounding offset; chroma predicts from
+// the reference on the existing chroma threads. Zero motion: each
+// sample's predictor is the sample it overwrites, so the recon planes
+// update in place (read ref, then write recon, same thread). A skip CTU
+// falls out of the cbf == 0 path (recon = pred = ref), and the left-column
+// LDS state refreshes from every CTU kind because every kind stores its
+// recon. An I job (slice_type != 1) in the same launch takes the intra
+// path only and produces what k_hevc_rows produces.
+// Sibling: everything outside the p_slice / inter branches is a copy of
+// k_hevc_rows above; a fix to either has to be made in both.
+struct RowsSharedP {
+  int lcolY[16];
+  int lcolCb[8];
+  int lcolCr[8];
+  int lfY[17];
+  short res[256];
+  int tmp[256];
+  short coef[256];
+  int pred[256];
+  int sad[5];        // DC, H, V, Planar, inter
+  int best;          // 0..3 intra mode index, 4 = inter
+  int cbf;
+  int predC[2][64];
+  short resC[2][64];
+  int tmpC[2][64];
+  short coefC[2][64];
+};
+
+__global__ __launch_bounds__(256) void k_hevc_rows_p(
+    const uint8_t* __restrict__ srcY, const uint8_t* __restrict__ srcCb,
+    const uint8_t* __restrict__ srcCr, int ypitch, int cpitch, int w, int h,
+    uint8_t* curY, uint8_t* curCb, uint8_t* curCr, int ctbw,
+    const HevcJob* __restrict__ jobs, int16_t* __restrict__ levels,
+    int* __restrict__ meta) {
+  // curY/curCb/curCr are read (reference) and written (recon): not
+  // __restrict__, unlike in k_hevc_rows
+  __shared__ RowsSharedP sh;
+  const HevcJob job = jobs[blockIdx.x];
+  const bool p_slice = job.slice_type == 1;
+  const int tid = threadIdx.x;
+  const int tx = tid & 15, ty = tid >> 4;
+  const int qp = job.qp, qpc = job.qpc;
+  const int y0 = job.ctu_row * 16;
+  const int cy0 = job.ctu_row * 8;
+  // visible chroma dims (CSC writes visible pixels only; clamped reads
+  // reproduce the CPU encoder's edge replication)
+  const int cw = (w + 1) >> 1, chh = (h + 1) >> 1;
+
+  for (int ci = 0; ci < job.seg_w; ++ci) {
+    const int cx = job.ctu_x0 + ci;
+    const int x0 = cx * 16;
+    const bool has_left = ci > 0;
+
+    // ---- load source pixel + build refs (closed forms; see header note)
+    const int sx_c = min(x0 + tx, w - 1), sy_c = min(y0 + ty, h - 1);
+    const int s = srcY[(size_t)sy_c * ypitch + sx_c];
+    // co-located reference sample: the recon plane still holds the
+    // previous coded picture here. Coded-size plane, unclamped. This
+    // thread is also the only writer of this sample (recon store below),
+    // so the read precedes every write of this CTU's recon.
+    const int r = p_slice ? curY[(size_t)(y0 + ty) * ypitch + x0 + tx] : 0;
+    if (tid < 16) {
+      int l = has_left ? sh.lcolY[tid] : 128;
+      // filtered column for planar: lf[i] = (l[i-1] + 2 l[i] + l[i+1]
+      // + 2) >> 2 with l[-1] = l[0] (corner replica), l[16] = l[15]
+      int lm = has_left ? sh.lcolY[tid == 0 ? 0 : tid - 1] : 128;
+      int lp = has_left ? sh.lcolY[tid == 15 ? 15 : tid + 1] : 128;
+      sh.lfY[tid] = (lm + 2 * l + lp + 2) >> 2;
+      if (tid == 15) sh.lfY[16] = has_left ? sh.lcolY[15] : 128;
+    }
+    if (tid < 5) sh.sad[tid] = 0;
+    __syncthreads();
+
+    const int l0 = has_left ? sh.lcolY[0] : 128;
+    const int lty = has_left ? sh.lcolY[ty] : 128;
+    const int l15 = has_left ? sh.lcolY[15] : 128;
+
+    // ---- 4 candidate predictions + SAD (order: DC, H, V, Planar)
+    int dcsum = 0;
+    if (tid == 0) {
+      dcsum = 16 * l0 + 16;
+      for (int i = 0; i < 16; ++i)
+        dcsum += has_left ? sh.lcolY[i] : 128;
+      sh.best = dcsum >> 5;  // stash DC value in best temporarily
+    }
+    __syncthreads();
+    const int dc = sh.best;
+    int pm[4];
+    // DC with luma edge filtering (§8.4.4.2.5, nT<32)
+    if (tx == 0 && ty == 0)
+      pm[0] = (lty + 2 * dc + l0 + 2) >> 2;
+    else if (ty == 0)
+      pm[0] = (l0 + 3 * dc + 2) >> 2;
+    else if (tx == 0)
+      pm[0] = (lty + 3 * dc + 2) >> 2;
+    else
+      pm[0] = dc;
+    // Horizontal: pred = left[y]; first-row edge adjust is identity here
+    // (top == corner == l0)
+    pm[1] = lty;
+    // Vertical: top is l0 everywhere; column-0 edge adjust
+    pm[2] = (tx == 0) ? clip8d(l0 + ((lty - l0) >> 1)) : l0;
+    // Planar on filtered refs. The [1 2 1] filter runs over the LINEAR
+    // reference array, where the replicated top/corner/below-left arms
+    // are flat — their filtered values stay the RAW l0 / l15; only the
+    // real left column smooths.
+    {
+      int lf = has_left ? sh.lfY[ty] : 128;
+      pm[3] = ((15 - tx) * lf + (tx + 1) * l0 + (15 - ty) * l0 +
+               (ty + 1) * l15 + 16) >> 5;
+    }
+    // wave-reduce SADs, then pick first strict-min in order DC,H,V,Planar
+    for (int m = 0; m < 4; ++m) {
+      int d = s - pm[m];
+      d = d < 0 ? -d : d;
+      for (int off = 32; off; off >>= 1) d += __shfl_down(d, off, 64);
+      if ((tid & 63) == 0) atomicAdd(&sh.sad[m], d);
+    }
+    if (p_slice) {
+      int d = s - r;
+      d = d < 0 ? -d : d;
+      for (int off = 32; off; off >>= 1) d += __shfl_down(d, off, 64);
+      if ((tid & 63) == 0) atomicAdd(&sh.sad[4], d);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int best = 0;
+      long bs = (long)sh.sad[0];
+      for (int m = 1; m < 4; ++m)
+        if ((long)sh.sad[m] < bs) {
+          bs = sh.sad[m];
+          best = m;
+        }
+      // inter iff sad_inter <= min(intra SADs)
+      if (p_slice && (long)sh.sad[4] <= bs) best = 4;
+      sh.best = best;
+    }
+    __syncthreads();
+    const int best = sh.best;
+    const bool inter = best == 4;
+    const int mode = inter ? 1 : kModeOrder[best];
+    const int p = inter ? r : pm[best];
+    // HM rounding: 171/512 intra, 85/512 inter, all three planes
+    const int qround = inter ? 85 : 171;
+    sh.pred[tid] = p;
+    sh.res[ty * 16 + tx] = (short)(s - p);
+    __syncthreads();
+
+    // ---- forward T16: stage1 over columns, stage2 over rows
+    {
+      int acc = 0;
+      // thread (u=ty, x=tx): sum_y T[u][y] * res[y][x]
+      for (int y = 0; y < 16; ++y) acc += cT16[ty][y] * sh.res[y * 16 + tx];
+      sh.tmp[ty * 16 + tx] = (acc + 4) >> 3;
+    }
+    __syncthreads();
+    {
+      int acc = 0;
+      // thread (u=ty, v=tx): sum_x tmp[u][x] * T[v][x]
+      for (int x = 0; x < 16; ++x) acc += sh.tmp[ty * 16 + x] * cT16[tx][x];
+      int coef = clip16d((acc + 512) >> 10);
+      // quant
+      const int qbits = 14 + qp / 6 + 3;
+      const int add = qround << (qbits - 9);
+      int a = coef < 0 ? -coef : coef;
+      int lv = (a * cQuantScale[qp % 6] + add) >> qbits;
+      if (lv > 32767) lv = 32767;
+      if (coef < 0) lv = -lv;
+      sh.coef[ty * 16 + tx] = (short)lv;
+      if (tid == 0) sh.cbf = 0;
+    }
+    __syncthreads();
+    {
+      int nz = sh.coef[tid] != 0;
+      if (__any(nz) && (tid & 63) == 0) atomicOr(&sh.cbf, 1);
+    }
+    __syncthreads();
+    const bool cbf_y = sh.cbf & 1;
+
+    // levels out
+    const size_t ctu_base =
+        (size_t)(job.ctu_row * ctbw + cx) * kHevcLevelsPerCtu;
+    levels[ctu_base + tid] = sh.coef[tid];
+
+    // ---- dequant + inverse + recon (only if cbf; else recon = pred)
+    int recon;
+    if (cbf_y) {
+      {
+        const int bd_shift = 7;
+        const long long scale =
+            ((long long)cDequantScale[qp % 6] << (qp / 6)) * 16;
+        long long d = ((long long)sh.coef[ty * 16 + tx] * scale +
+                       (1 << (bd_shift - 1))) >> bd_shift;
+        sh.tmp[ty * 16 + tx] = clip16d((int)d);
+      }
+      __syncthreads();
+      // reuse res as stage buffer: stage1 (y=ty, v=tx)
+      {
+        int acc = 0;
+        for (int u = 0; u < 16; ++u)
+          acc += cT16[u][ty] * sh.tmp[u * 16 + tx];
+        sh.res[ty * 16 + tx] = (short)clip16d((acc + 64) >> 7);
+      }
+      __syncthreads();
+      {
+        int acc = 0;
+        for (int v = 0; v < 16; ++v)
+          acc += sh.res[ty * 16 + v] * cT16[v][tx];
+        recon = clip8d(sh.pred[tid] + clip16d((acc + 2048) >> 12));
+      }
+    } else {
+      recon = p;
+    }
+    __syncthreads();
+    curY[(size_t)(y0 + ty) * ypitch + x0 + tx] = (uint8_t)recon;
+    if (tx == 15) sh.lcolY[ty] = recon;
+
+    // ---- chroma: plane pl = 0 (Cb, threads 0..63) / 1 (Cr, 64..127)
+    const int cpl = tid >> 6;          // 0..3 (waves)
+    if (cpl < 2) {
+      const int ctid = tid & 63;
+      const int ctx8 = ctid & 7, cty8 = ctid >> 3;
+      const uint8_t* srcC = cpl ? srcCr : srcCb;
+      int* lcol = cpl ? sh.lcolCr : sh.lcolCb;
+      const int cx0 = cx * 8;
+      const int cs = srcC[(size_t)min(cy0 + cty8, chh - 1) * cpitch +
+                          min(cx0 + ctx8, cw - 1)];
+      const int cl0 = has_left ? lcol[0] : 128;
+      const int clty = has_left ? lcol[cty8] : 128;
+      const int cl7 = has_left ? lcol[7] : 128;
+      int cp;
+      if (inter) {
+        // zero-motion chroma predictor: the sample this thread overwrites
+        // in the chroma recon store below (same ctid -> same address)
+        const uint8_t* refC = cpl ? curCr : curCb;
+        cp = refC[(size_t)(cy0 + cty8) * cpitch + cx0 + ctx8];
+      } else if (mode == 1) {  // DC: no chroma edge filter
+        int sum = 8 * cl0 + 8;
+        for (int i = 0; i < 8; ++i) sum += has_left ? lcol[i] : 128;
+        cp = sum >> 4;
+      } else if (mode == 10) {
+        cp = clty;
+      } else if (mode == 26) {
+        cp = cl0;
+      } else {  // planar (unfiltered refs for chroma)
+        cp = ((7 - ctx8) * clty + (ctx8 + 1) * cl0 + (7 - cty8) * cl0 +
+              (cty8 + 1) * cl7 + 8) >> 4;
+      }
+      sh.predC[cpl][ctid] = cp;
+      sh.resC[cpl][cty8 * 8 + ctx8] = (short)(cs - cp);
+    }
+    __syncthreads();
+    if (cpl < 2) {
+      const int ctid = tid & 63;
+      const int u8 = ctid >> 3, x8 = ctid & 7;
+      int acc = 0;
+      for (int y = 0; y < 8; ++y)
+        acc += cT8[u8][y] * sh.resC[cpl][y * 8 + x8];
+      sh.tmpC[cpl][u8 * 8 + x8] = (acc + 2) >> 2;
+    }
+    __syncthreads();
+    if (cpl < 2) {
+      const int ctid = tid & 63;
+      const int u8 = ctid >> 3, v8 = ctid & 7;
+      int acc = 0;
+      for (int x = 0; x < 8; ++x)
+        acc += sh.tmpC[cpl][u8 * 8 + x] * cT8[v8][x];
+      int coef = clip16d((acc + 256) >> 9);
+      const int qbits = 14 + qpc / 6 + 4;
+      const int add = qround << (qbits - 9);
+      int a = coef < 0 ? -coef : coef;
+      int lv = (a * cQuantScale[qpc % 6] + add) >> qbits;
+      if (lv > 32767) lv = 32767;
+      if (coef < 0) lv = -lv;
+      sh.coefC[cpl][u8 * 8 + v8] = (short)lv;
+    }
+    __syncthreads();
+    if (cpl < 2) {
+      const int ctid = tid & 63;
+      int nz = sh.coefC[cpl][ctid] != 0;
+      if (__any(nz) && ctid == 0) atomicOr(&sh.cbf, 2 << cpl);
+      levels[ctu_base + 256 + cpl * 64 + ctid] = sh.coefC[cpl][ctid];
+    }
+    __syncthreads();
+    // chroma dequant + inverse: barriers at top level (uniform), work
+    // guarded per-thread
+    {
+      const int ctid = tid & 63;
+      const int y8 = ctid >> 3, x8 = ctid & 7;
+      const int cbf_c = cpl < 2 ? ((sh.cbf >> (1 + cpl)) & 1) : 0;
+      if (cbf_c) {
+        const int bd_shift = 6;
+        const long long scale =
+            ((long long)cDequantScale[qpc % 6] << (qpc / 6)) * 16;
+        long long d = ((long long)sh.coefC[cpl][y8 * 8 + x8] * scale +
+                       (1 << (bd_shift - 1))) >> bd_shift;
+        sh.tmpC[cpl][y8 * 8 + x8] = clip16d((int)d);
+      }
+      __syncthreads();
+      if (cbf_c) {
+        int acc = 0;
+        for (int u = 0; u < 8; ++u)
+          acc += cT8[u][y8] * sh.tmpC[cpl][u * 8 + x8];
+        sh.resC[cpl][y8 * 8 + x8] = (short)clip16d((acc + 64) >> 7);
+      }
+      __syncthreads();
+      if (cpl < 2) {
+        int creconv;
+        if (cbf_c) {
+          int acc = 0;
+          for (int v = 0; v < 8; ++v)
+            acc += sh.resC[cpl][y8 * 8 + v] * cT8[v][x8];
+          creconv = clip8d(sh.predC[cpl][ctid] +
+                           clip16d((acc + 2048) >> 12));
+        } else {
+          creconv = sh.predC[cpl][ctid];
+        }
+        uint8_t* curC = cpl ? curCr : curCb;
+        curC[(size_t)(cy0 + y8) * cpitch + cx * 8 + x8] = (uint8_t)creconv;
+        int* lcol = cpl ? sh.lcolCr : sh.lcolCb;
+        if (x8 == 7) lcol[y8] = creconv;
+      }
+    }
+    __syncthreads();
+    if (tid == 0) {
+      // inter with no coded residual is a skip (recon == reference)
+      meta[(size_t)(job.ctu_row * ctbw + cx) * kHevcMetaPerCtu + 0] =
+          !inter ? mode : sh.cbf ? kHevcMetaMerge : kHevcMetaSkip;
+      meta[(size_t)(job.ctu_row * ctbw + cx) * kHevcMetaPerCtu + 1] = sh.cbf;
+    }
+    __syncthreads();
+  }
+}
+
 void launch_hevc_rows(const uint8_t* d_srcY, const uint8_t* d_srcCb,
                       const uint8_t* d_srcCr, int ypitch, int cpitch, int w,
                       int h, uint8_t* d_curY, uint8_t* d_curCb,
@@ -382,6 +727,18 @@ void launch_hevc_rows(const uint8_t* d_srcY, const uint8_t* d_srcCb,
                       hipStream_t stream) {
   if (n_jobs == 0) return;
   hipLaunchKernelGGL(k_hevc_rows, dim3(n_jobs), dim3(256), 0, stream,
+                     d_srcY, d_srcCb, d_srcCr, ypitch, cpitch, w, h, d_curY,
+                     d_curCb, d_curCr, ctbw, d_jobs, d_levels, d_meta);
+}
+
+void launch_hevc_rows_p(const uint8_t* d_srcY, const uint8_t* d_srcCb,
+                        const uint8_t* d_srcCr, int ypitch, int cpitch, int w,
+                        int h, uint8_t* d_curY, uint8_t* d_curCb,
+                        uint8_t* d_curCr, int ctbw, int n_jobs,
+                        const HevcJob* d_jobs, int16_t* d_levels, int* d_meta,
+                        hipStream_t stream) {
+  if (n_jobs == 0) return;
+  hipLaunchKernelGGL(k_hevc_rows_p, dim3(n_jobs), dim3(256), 0, stream,
                      d_srcY, d_srcCb, d_srcCr, ypitch, cpitch, w, h, d_curY,
                      d_curCb, d_curCr, ctbw, d_jobs, d_levels, d_meta);
 }
@@ -1019,6 +1376,8 @@ __device__ void dev_code_residual(DevCabac& cab, uint32_t* ctx_lds, int lane,
 
 // F444: the chroma TBs are 16x16 at lv + 256 / lv + 512 (hevc_gpu_layout.h)
 // and go through the same dev_code_residual<16> as luma with cidx 1 / 2.
+// Sibling: dev_code_ctu_p below repeats the MPM and remainder coding of
+// this function; a fix here has to be made there too.
 template <bool F444>
 __device__ void dev_code_ctu(DevCabac& cab, uint32_t* ctx_lds, int lane,
                              int mode, int left_mode, int cbf_mask,
@@ -1134,6 +1493,192 @@ __global__ __launch_bounds__(64) void k_hevc_cabac(
   counts[j * 3 + 0] = cab.count;
   counts[j * 3 + 1] = tail & 0xFFFF;
   counts[j * 3 + 2] = tail >> 16;
+}
+
+// ---- CABAC kernel, P pictures --------------------------------------------
+// Sibling of k_hevc_cabac<false> for frames that hold P jobs, same
+// one-job-per-wave, lane-0 design. The bank grows by the six P-only
+// contexts (appended, so the shared offsets above hold), initType follows
+// job.slice_type, and the CTU loop carries left-is-skip and
+// left-intra-mode. Transliterates entropy.h code_ctu_syntax_p; an I job in
+// the same launch codes exactly the k_hevc_cabac<false> bins. The
+// residual coder is instantiated apart (kInst 2) so the I kernels'
+// inlining is not disturbed.
+#define HG_CTX_SKIP 123
+#define HG_CTX_PREDMODE 126
+#define HG_CTX_PARTMODE 127
+#define HG_CTX_MERGE 128
+#define HG_NUM_CTX_P 129
+
+// initType 1 (P slices, cabac_init_flag 0); mirrors tables.h kInit1*
+__constant__ uint8_t cInitVals1[HG_NUM_CTX_P] = {
+    // split_cu (3)
+    107, 139, 126,
+    // prev_intra (1), chroma_mode (1)
+    154, 152,
+    // cbf_luma (2)
+    153, 111,
+    // cbf_chroma (4)
+    149, 107, 167, 154,
+    // last_x (18)
+    125, 110, 94, 110, 95, 79, 125, 111, 110, 78, 110, 111, 111, 95, 94,
+    108, 123, 108,
+    // last_y (18)
+    125, 110, 94, 110, 95, 79, 125, 111, 110, 78, 110, 111, 111, 95, 94,
+    108, 123, 108,
+    // csbf (4)
+    121, 140, 61, 154,
+    // sig (42)
+    155, 154, 139, 153, 139, 123, 123, 63, 153, 166, 183, 140, 136, 153,
+    154, 166, 183, 140, 136, 153, 154, 166, 183, 140, 136, 153, 154, 170,
+    153, 123, 123, 107, 121, 107, 121, 167, 151, 183, 140, 151, 183, 140,
+    // gt1 (24)
+    154, 196, 196, 167, 154, 152, 167, 182, 182, 134, 149, 136, 153, 121,
+    136, 137, 169, 194, 166, 167, 154, 167, 137, 182,
+    // gt2 (6)
+    107, 167, 91, 122, 107, 167,
+    // cu_skip (3), pred_mode (1), part_mode bin 0 (1), merge_flag (1)
+    197, 185, 201, 149, 154, 110};
+
+// kind: intra mode 0..34, kHevcMetaMerge or kHevcMetaSkip (meta +0).
+// Sibling: the intra branch copies dev_code_ctu<false> above (MPM list,
+// remainder); a fix to either has to be made in both.
+// left_mode < 0: left CTU absent or not intra.
+__device__ void dev_code_ctu_p(DevCabac& cab, uint32_t* ctx_lds, int lane,
+                               bool p_slice, int kind, bool left_skip,
+                               int left_mode, int cbf_mask,
+                               const int16_t* __restrict__ lv) {
+  cab.bin(&CTX_LDS(HG_CTX_SPLIT), 0);
+  bool code_cbf_y = true;
+  if (p_slice) {
+    cab.bin(&CTX_LDS(HG_CTX_SKIP + (left_skip ? 1 : 0)),
+            kind == kHevcMetaSkip ? 1 : 0);
+    if (kind == kHevcMetaSkip) return;
+    cab.bin(&CTX_LDS(HG_CTX_PREDMODE), kind < 35 ? 1 : 0);
+  }
+  if (kind < 35) {
+    const int mode = kind;
+    int cand_a = left_mode >= 0 ? left_mode : 1;
+    int cand_b = 1;
+    int list[3];
+    if (cand_a == cand_b) {
+      if (cand_a < 2) {
+        list[0] = 0;
+        list[1] = 1;
+        list[2] = 26;
+      } else {
+        list[0] = cand_a;
+        list[1] = 2 + ((cand_a + 29) % 32);
+        list[2] = 2 + ((cand_a - 2 + 1) % 32);
+      }
+    } else {
+      list[0] = cand_a;
+      list[1] = cand_b;
+      list[2] = (cand_a != 0 && cand_b != 0) ? 0
+                : (cand_a != 1 && cand_b != 1) ? 1
+                                               : 26;
+    }
+    int mpm_idx = -1;
+    for (int i = 0; i < 3; ++i)
+      if (list[i] == mode) {
+        mpm_idx = i;
+        break;
+      }
+    cab.bin(&CTX_LDS(HG_CTX_PREVINTRA), mpm_idx >= 0 ? 1 : 0);
+    if (mpm_idx >= 0) {
+      cab.bypass(mpm_idx > 0 ? 1 : 0);
+      if (mpm_idx > 0) cab.bypass(mpm_idx - 1);
+    } else {
+      int a = list[0], b = list[1], c = list[2], t;
+      if (a > b) { t = a; a = b; b = t; }
+      if (b > c) { t = b; b = c; c = t; }
+      if (a > b) { t = a; a = b; b = t; }
+      int rem = mode;
+      if (mode > c) --rem;
+      if (mode > b) --rem;
+      if (mode > a) --rem;
+      cab.bypass_bins(rem, 5);
+    }
+    cab.bin(&CTX_LDS(HG_CTX_CHROMA), 0);
+  } else {
+    cab.bin(&CTX_LDS(HG_CTX_PARTMODE), 1);   // 2Nx2N
+    cab.bin(&CTX_LDS(HG_CTX_MERGE), 1);      // merge_flag; no merge_idx
+    // rqt_root_cbf not coded (2Nx2N merge); cbf_luma inferred 1 unless
+    // a chroma cbf is set
+    code_cbf_y = (cbf_mask & 6) != 0;
+  }
+  cab.bin(&CTX_LDS(HG_CTX_CBFC), (cbf_mask >> 1) & 1);
+  cab.bin(&CTX_LDS(HG_CTX_CBFC), (cbf_mask >> 2) & 1);
+  if (code_cbf_y) cab.bin(&CTX_LDS(HG_CTX_CBFY + 1), cbf_mask & 1);
+  if (cbf_mask & 1) dev_code_residual<16, 2>(cab, ctx_lds, lane, lv, 0);
+  if (cbf_mask & 2) dev_code_residual<8, 2>(cab, ctx_lds, lane, lv + 256, 1);
+  if (cbf_mask & 4) dev_code_residual<8, 2>(cab, ctx_lds, lane, lv + 320, 2);
+}
+
+__global__ __launch_bounds__(64) void k_hevc_cabac_p(
+    const int16_t* __restrict__ levels, const int* __restrict__ meta,
+    int ctbw, int n_jobs, const HevcJob* __restrict__ jobs,
+    uint8_t* __restrict__ out, int out_stride, int* __restrict__ counts) {
+  __shared__ uint32_t ctx_lds[HG_NUM_CTX_P];
+  __shared__ uint32_t ptab[256];   // packed (state, qRangeIdx) entries
+  const int lane = threadIdx.x;
+  const int j = blockIdx.x;
+  if (j >= n_jobs) return;
+
+  const HevcJob job = jobs[j];
+  const bool p_slice = job.slice_type == 1;
+  const int qp = job.qp < 0 ? 0 : job.qp > 51 ? 51 : job.qp;
+  for (int i = lane; i < 256; i += 64) {
+    const int state = i >> 2, q = i & 3;
+    const uint32_t lps = cRangeTabLps[state][q];
+    const uint32_t nlps = cTransIdxLps[state];
+    const uint32_t nmps = state < 62 ? state + 1 : state;
+    ptab[i] = lps | (nlps << 8) | (nmps << 14)
+              | ((uint32_t)cRenorm[lps >> 3] << 20);
+  }
+  for (int i = lane; i < HG_NUM_CTX_P; i += 64) {
+    // an I slice never touches the P-only contexts; 154 keeps them defined
+    int iv = p_slice ? cInitVals1[i] : i < HG_NUM_CTX ? cInitVals[i] : 154;
+    int slope = (iv >> 4) * 5 - 45;
+    int off = ((iv & 15) << 3) - 16;
+    int pre = ((slope * qp) >> 4) + off;
+    pre = pre < 1 ? 1 : pre > 126 ? 126 : pre;
+    ctx_lds[i] = pre <= 63 ? (uint32_t)((63 - pre) << 1)
+                           : (uint32_t)(((pre - 64) << 1) | 1);
+  }
+  __syncthreads();
+  if (lane != 0) return;
+
+  DevCabac cab;
+  cab.init(out + (size_t)j * out_stride);
+  cab.ptab = ptab;
+  int left_mode = -1;
+  bool left_skip = false;
+  for (int ci = 0; ci < job.seg_w; ++ci) {
+    const int cx = job.ctu_x0 + ci;
+    const size_t mbase = (size_t)(job.ctu_row * ctbw + cx);
+    const int kind = meta[mbase * kHevcMetaPerCtu + 0];
+    const int cbf = meta[mbase * kHevcMetaPerCtu + 1];
+    dev_code_ctu_p(cab, ctx_lds, lane, p_slice, kind, left_skip, left_mode,
+                   cbf, levels + mbase * kHevcLevelsPerCtu);
+    left_skip = kind == kHevcMetaSkip;
+    left_mode = kind < 35 ? kind : -1;
+    cab.terminate(ci == job.seg_w - 1 ? 1 : 0);
+  }
+  int tail = cab.finish();
+  counts[j * 3 + 0] = cab.count;
+  counts[j * 3 + 1] = tail & 0xFFFF;
+  counts[j * 3 + 2] = tail >> 16;
+}
+
+void launch_hevc_cabac_p(const int16_t* d_levels, const int* d_meta, int ctbw,
+                         int n_jobs, const HevcJob* d_jobs, uint8_t* d_out,
+                         int out_stride_bytes, int* d_counts,
+                         hipStream_t stream) {
+  if (n_jobs == 0) return;
+  hipLaunchKernelGGL(k_hevc_cabac_p, dim3(n_jobs), dim3(64), 0, stream,
+                     d_levels, d_meta, ctbw, n_jobs, d_jobs, d_out,
+                     out_stride_bytes, d_counts);
 }
 
 void launch_hevc_cabac(const int16_t* d_levels, const int* d_meta, int ctbw,

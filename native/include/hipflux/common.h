@@ -53,6 +53,7 @@ struct CaptureSettings {
                                     // (throughput mode; emission lags one
                                     // frame — recording/transcode use)
   bool video_fullcolor = false;     // 4:4:4
+  bool hevc_inter = false;          // HEVC: zero-motion P stripes (4:2:0)
   bool use_paint_over_quality = true;
   int paint_over_trigger_frames = 15;
   int video_paintover_crf = 18;

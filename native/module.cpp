@@ -1,6 +1,8 @@
 // pybind11 bindings: the `hipflux._native` module.
 // API surface mirrors the pixelflux contract the reference control plane
 // consumes.
+#include <algorithm>
+
 #include <pybind11/functional.h>
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
@@ -61,6 +63,7 @@ PYBIND11_MODULE(_native, m) {
       .def_readwrite("video_streaming_mode", &CaptureSettings::video_streaming_mode)
       .def_readwrite("video_deblock", &CaptureSettings::video_deblock)
       .def_readwrite("video_fullcolor", &CaptureSettings::video_fullcolor)
+      .def_readwrite("hevc_inter", &CaptureSettings::hevc_inter)
       .def_readwrite("use_paint_over_quality", &CaptureSettings::use_paint_over_quality)
       .def_readwrite("paint_over_trigger_frames", &CaptureSettings::paint_over_trigger_frames)
       .def_readwrite("video_paintover_crf", &CaptureSettings::video_paintover_crf)
@@ -498,7 +501,12 @@ PYBIND11_MODULE(_native, m) {
       "_pipeline_encode",
       [](const std::string& kind, py::list frames, int w, int h, int qp,
          int stripe_h, int output_mode, bool dump, bool fullcolor,
-         int pipeline_depth, py::object encode_mask) -> py::object {
+         int pipeline_depth, py::object encode_mask, bool hevc_inter,
+         py::object idr_frames) -> py::object {
+        std::vector<size_t> idr_at;
+        if (!idr_frames.is_none())
+          for (py::handle v : idr_frames.cast<py::list>())
+            idr_at.push_back(v.cast<size_t>());
         // optional damage mask: mask[frame][stripe] -> StripeJob.encode
         const size_t n_stripes =
             stripe_h > 0 ? static_cast<size_t>((h + stripe_h - 1) / stripe_h)
@@ -530,6 +538,7 @@ PYBIND11_MODULE(_native, m) {
         s.video_crf = qp;
         s.jpeg_quality = qp;
         s.video_fullcolor = fullcolor;
+        s.hevc_inter = hevc_inter;
         s.use_cpu = kind == "cpu";
         s.gpu_id = kind == "cpu" ? -1 : 0;
         std::unique_ptr<EncodePipeline> p;
@@ -565,7 +574,8 @@ PYBIND11_MODULE(_native, m) {
           f.ts_ms = now_ms();
           FrameContext ctx;
           ctx.frame_id = static_cast<uint32_t>(i);
-          ctx.idr = (i == 0);
+          ctx.idr = (i == 0) || std::find(idr_at.begin(), idr_at.end(), i) !=
+                                    idr_at.end();
           ctx.crf = qp;
           ctx.jpeg_quality = qp;
           for (int y = 0; y < h; y += stripe_h) {
@@ -607,9 +617,23 @@ PYBIND11_MODULE(_native, m) {
       py::arg("qp") = 26, py::arg("stripe_h") = 64,
       py::arg("output_mode") = 1, py::arg("dump") = false,
       py::arg("fullcolor") = false, py::arg("pipeline_depth") = 1,
-      py::arg("encode_mask") = py::none(),
+      py::arg("encode_mask") = py::none(), py::arg("hevc_inter") = false,
+      py::arg("idr_frames") = py::none(),
       "Test hook: run frames through a named encode pipeline. "
-      "encode_mask[frame][stripe] (optional) gates which stripes encode.");
+      "encode_mask[frame][stripe] (optional) gates which stripes encode. "
+      "hevc_inter turns on HEVC P stripes; idr_frames lists frame indices "
+      "that request an IDR besides frame 0.");
+
+  m.def(
+      "_hevc_init_values",
+      [](int init_type) {
+        uint8_t iv[hevc::kNumContextsP];
+        hevc::fill_init_values(init_type, iv);
+        return py::bytes(reinterpret_cast<const char*>(iv), sizeof(iv));
+      },
+      py::arg("init_type"),
+      "Test hook: the HEVC CABAC initValues of one initType in context-bank "
+      "order (native/cpu/hevc/tables.h CtxOffset).");
 
   // ---- persistent pipeline handle for benchmarking ------------------------
   struct BenchPipeline {
@@ -635,7 +659,7 @@ PYBIND11_MODULE(_native, m) {
     }
     BenchPipeline(const std::string& kind, int width, int height, int qp_,
                   int stripe, int output_mode, int gpu_id,
-                  int pipeline_depth, bool fullcolor)
+                  int pipeline_depth, bool fullcolor, bool hevc_inter)
         : w(width), h(height), qp(qp_), stripe_h(stripe) {
       CaptureSettings s;
       s.capture_width = w;
@@ -646,6 +670,7 @@ PYBIND11_MODULE(_native, m) {
       s.jpeg_quality = qp;
       s.gpu_id = gpu_id;
       s.video_fullcolor = fullcolor;
+      s.hevc_inter = hevc_inter;
       s.use_cpu = kind == "cpu";
       if (kind == "gpu") {
         p = make_hip_pipeline(s);
@@ -660,11 +685,12 @@ PYBIND11_MODULE(_native, m) {
   };
   py::class_<BenchPipeline>(m, "BenchPipeline")
       .def(py::init<const std::string&, int, int, int, int, int, int,
-                    int, bool>(),
+                    int, bool, bool>(),
            py::arg("kind"), py::arg("width"), py::arg("height"),
            py::arg("qp") = 28, py::arg("stripe_height") = 64,
            py::arg("output_mode") = 1, py::arg("gpu_id") = 0,
-           py::arg("pipeline_depth") = 1, py::arg("fullcolor") = false)
+           py::arg("pipeline_depth") = 1, py::arg("fullcolor") = false,
+           py::arg("hevc_inter") = false)
       .def_property_readonly("pipeline",
                              [](BenchPipeline& b) { return b.p->name(); })
       .def_readonly("last_frame_id", &BenchPipeline::last_frame_id)

@@ -1,9 +1,12 @@
 // CPU striped HEVC pipeline: one independent hevc::StripeEncoder (own
 // bitstream, recon state) per stripe, encoded in parallel on the pool.
-// All-intra (every stripe emission is an IDR), so every stripe is a
-// keyframe and reference-chain repair never applies. Bit-exact reference
-// for the HIP HEVC pipeline.
+// All-intra by default (every stripe emission is an IDR and a key
+// stripe). With settings.hevc_inter (4:2:0 only) a stripe's emissions
+// after its first are P pictures referencing its previous coded picture,
+// until ctx.idr; each encoder keeps its own {have_ref, poc}, rebuilt on a
+// size change. Bit-exact reference for the HIP HEVC pipeline.
 #include <algorithm>
+#include <cstdio>
 
 #include "cpu/h264/encoder.h"  // bgrx_to_yuv420 (shared CSC reference)
 #include "cpu/hevc/encoder.h"
@@ -17,7 +20,12 @@ class CpuHevcPipeline : public EncodePipeline {
  public:
   explicit CpuHevcPipeline(const CaptureSettings& s)
       : settings_(s),
-        pool_(std::max(2u, std::thread::hardware_concurrency() / 2)) {}
+        pool_(std::max(2u, std::thread::hardware_concurrency() / 2)) {
+    if (s.hevc_inter && s.video_fullcolor)
+      std::fprintf(stderr,
+                   "[cpu-hevc] hevc_inter is 4:2:0 only; video_fullcolor "
+                   "stays all-intra\n");
+  }
 
   void encode_frame(const RawFrame& frame, const FrameContext& ctx,
                     const Emit& emit) override {
@@ -31,7 +39,8 @@ class CpuHevcPipeline : public EncodePipeline {
         int y0 = static_cast<int>(i) * stripe_h;
         int hgt = std::min(stripe_h, frame.height - y0);
         encoders_.push_back(std::make_unique<hevc::StripeEncoder>(
-            frame.width, hgt, hevc::default_slices_per_row(frame.width), fc));
+            frame.width, hgt, hevc::default_slices_per_row(frame.width), fc,
+            settings_.hevc_inter && !fc));
       }
       ypitch_ = (frame.width + 15) & ~15;
       cpitch_ = fc ? ypitch_ : ypitch_ / 2;
@@ -45,6 +54,7 @@ class CpuHevcPipeline : public EncodePipeline {
       std::vector<uint8_t> bytes;
       int y0 = 0, h = 0;
       bool encode = false;
+      bool idr = true;
     };
     std::vector<Out> outs(ctx.stripes.size());
     for (size_t i = 0; i < ctx.stripes.size(); ++i) {
@@ -68,8 +78,10 @@ class CpuHevcPipeline : public EncodePipeline {
           h264::bgrx_to_yuv420(
               frame.data + static_cast<size_t>(j.y0) * frame.stride,
               frame.stride, frame.width, hgt, y, ypitch_, cb, cr, cpitch_);
+        hevc::EncodeStats st;
         encoders_[i]->encode_frame(y, ypitch_, cb, cr, cpitch_, ctx.crf,
-                                   outs[i].bytes);
+                                   outs[i].bytes, &st, ctx.idr);
+        outs[i].idr = st.idr;
       });
     }
     pool_.wait_all();
@@ -83,7 +95,7 @@ class CpuHevcPipeline : public EncodePipeline {
       s.y = o.y0;
       s.width = w_;
       s.height = o.h;
-      s.is_keyframe = true;   // all-intra: every emission is an IDR
+      s.is_keyframe = o.idr;  // P emissions carry no parameter sets
       emit(s);
     }
   }

@@ -5,6 +5,10 @@
 // Byte-identical to CpuHevcPipeline (asserted by tests/test_gpu_hevc.py);
 // HIPFLUX_CPU_HEVC_ENTROPY=1 swaps the CABAC kernel for the host entropy
 // coder over D2H levels/meta to isolate rows-kernel vs entropy bugs.
+// settings.hevc_inter (4:2:0 only): a stripe's emissions after its first
+// are P pictures (zero-motion merge/skip + intra CTUs) against its
+// previous coded picture, which is the recon planes themselves, updated
+// in place by the rows kernel. Per-stripe {have_ref, poc} live here.
 #include <cstdio>
 #include <cstdlib>
 
@@ -29,7 +33,11 @@ class HipHevcPipeline : public EncodePipeline {
 
   explicit HipHevcPipeline(const CaptureSettings& s)
       : settings_(s), pool_(encode_pool_threads()), dev_(s.gpu_id),
-        fc_(s.video_fullcolor) {
+        fc_(s.video_fullcolor), inter_(s.hevc_inter && !s.video_fullcolor) {
+    if (s.hevc_inter && s.video_fullcolor)
+      std::fprintf(stderr,
+                   "[hip-hevc] hevc_inter is 4:2:0 only; video_fullcolor "
+                   "stays all-intra\n");
     cpu_entropy_ = std::getenv("HIPFLUX_CPU_HEVC_ENTROPY") != nullptr;
     timing_ = std::getenv("HIPFLUX_TIMES") != nullptr;
     stripe_h_ = std::max(16, s.stripe_height & ~15);
@@ -39,6 +47,12 @@ class HipHevcPipeline : public EncodePipeline {
   struct StripeRef {
     int y0, vis_h;      // pixels
     int job0, jobn;     // job index range
+    bool idr;           // IDR emission (parameter sets, key stripe)
+  };
+  // Temporal state of one stripe position (index into ctx.stripes).
+  struct StripeState {
+    bool have_ref = false;   // recon planes hold its previous coded picture
+    int poc = 0;             // POC of its next picture (0 after an IDR)
   };
   struct Pending {
     bool active = false;
@@ -63,7 +77,11 @@ class HipHevcPipeline : public EncodePipeline {
     const size_t frame_bytes = static_cast<size_t>(frame.stride) * frame.height;
     // frame N+1's upload/CSC/rows run on rows_stream_, concurrent with
     // frame N's CABAC on stream_ (levels/meta are parity
-    // double-buffered; the recon planes have no cross-frame reader)
+    // double-buffered). Without hevc_inter the recon planes have no
+    // cross-frame reader. With it, the rows kernel of frame N+1 reads the
+    // recon that the rows kernel of frame N wrote: both run on
+    // rows_stream_, so at depth 2 frame N+1's rows follow frame N's rows
+    // in stream order and no other stream touches the planes.
     if (frame.dev)   // front-end frame: already complete on the device
       HIP_CHECK(hipMemcpyAsync(d_frame_[par], frame.dev, frame_bytes,
                                hipMemcpyDeviceToDevice, rows_stream_));
@@ -83,6 +101,9 @@ class HipHevcPipeline : public EncodePipeline {
     pd.frame_id = ctx.frame_id;
     pd.ts_ms = frame.ts_ms;
     int n_jobs = 0;
+    bool any_p = false;
+    if (sstate_.size() != ctx.stripes.size())
+      sstate_.assign(ctx.stripes.size(), StripeState{});
     const int spr = hevc::default_slices_per_row(w_);
     for (size_t i = 0; i < ctx.stripes.size(); ++i) {
       const auto& st = ctx.stripes[i];
@@ -93,7 +114,11 @@ class HipHevcPipeline : public EncodePipeline {
       int addr_bits = 1;
       while ((1 << addr_bits) < n_ctb) ++addr_bits;
       const int per = (ctbw_ + spr - 1) / spr;
-      StripeRef sr{st.y0, vis_h, n_jobs, 0};
+      StripeState& ss = sstate_[i];
+      const bool p_pic = inter_ && ss.have_ref && !ctx.idr;
+      if (!p_pic) ss.poc = 0;
+      any_p |= p_pic;
+      StripeRef sr{st.y0, vis_h, n_jobs, 0, !p_pic};
       for (int r = 0; r < s_ctb_h; ++r) {
         for (int s0 = 0; s0 < ctbw_; s0 += per) {
           auto& j = h_jobs_[par][n_jobs++];
@@ -106,8 +131,13 @@ class HipHevcPipeline : public EncodePipeline {
           j.slice_addr = r * ctbw_ + s0;
           j.addr_bits = addr_bits;
           j.last_in_pic = 0;
+          j.slice_type = p_pic ? 1 : 2;
+          j.poc_lsb = ss.poc & 255;
         }
       }
+      // POC counts this stripe's own coded pictures
+      ++ss.poc;
+      ss.have_ref = true;
       sr.jobn = n_jobs;
       pd.stripes.push_back(sr);
     }
@@ -125,6 +155,13 @@ class HipHevcPipeline : public EncodePipeline {
                                    h_, d_curY_, d_curCb_, d_curCr_, ctbw_,
                                    n_jobs, d_jobs_[par], d_levels_[par],
                                    d_meta_[par], rows_stream_);
+    else if (any_p)
+      // I and P jobs of one frame share one launch that branches per job;
+      // a frame with no P job keeps the unchanged I kernels
+      hevcgpu::launch_hevc_rows_p(d_srcY_, d_srcCb_, d_srcCr_, ypitch_,
+                                  cpitch_, w_, h_, d_curY_, d_curCb_,
+                                  d_curCr_, ctbw_, n_jobs, d_jobs_[par],
+                                  d_levels_[par], d_meta_[par], rows_stream_);
     else
       hevcgpu::launch_hevc_rows(d_srcY_, d_srcCb_, d_srcCr_, ypitch_,
                                 cpitch_, w_, h_, d_curY_, d_curCb_, d_curCr_,
@@ -141,9 +178,14 @@ class HipHevcPipeline : public EncodePipeline {
       return pd;
     }
     if (timing_) HIP_CHECK(hipEventRecord(ev_t_[1], stream_));
-    hevcgpu::launch_hevc_cabac(d_levels_[par], d_meta_[par], ctbw_, n_jobs,
-                               d_jobs_[par], d_out_[par], out_stride_,
-                               d_counts_[par], stream_, fc_);
+    if (any_p)
+      hevcgpu::launch_hevc_cabac_p(d_levels_[par], d_meta_[par], ctbw_,
+                                   n_jobs, d_jobs_[par], d_out_[par],
+                                   out_stride_, d_counts_[par], stream_);
+    else
+      hevcgpu::launch_hevc_cabac(d_levels_[par], d_meta_[par], ctbw_, n_jobs,
+                                 d_jobs_[par], d_out_[par], out_stride_,
+                                 d_counts_[par], stream_, fc_);
     if (timing_) HIP_CHECK(hipEventRecord(ev_t_[2], stream_));
     HIP_CHECK(hipMemcpyAsync(h_counts_[par], d_counts_[par],
                              sizeof(int) * 3 * n_jobs,
@@ -187,6 +229,7 @@ class HipHevcPipeline : public EncodePipeline {
     struct SOut {
       std::vector<uint8_t> bytes;
       int y0, vis_h;
+      bool idr;
     };
     std::vector<SOut> outs(pd.stripes.size());
     for (size_t si = 0; si < pd.stripes.size(); ++si) {
@@ -196,8 +239,10 @@ class HipHevcPipeline : public EncodePipeline {
         o.y0 = sr.y0;
         o.vis_h = sr.vis_h;
         const int coded_h = (sr.vis_h + 15) & ~15;
-        hevc::write_hevc_stripe_headers(ctbw_ * 16, coded_h, w_, sr.vis_h,
-                                        o.bytes, fc_);
+        o.idr = sr.idr;
+        if (sr.idr)   // P emissions carry no parameter sets
+          hevc::write_hevc_stripe_headers(ctbw_ * 16, coded_h, w_, sr.vis_h,
+                                          o.bytes, fc_, inter_);
         for (int j = sr.job0; j < sr.jobn; ++j) {
           const auto& job = h_jobs_[par][j];
           if (cpu_entropy_) {
@@ -205,13 +250,15 @@ class HipHevcPipeline : public EncodePipeline {
                                       job.ctu_row, job.ctu_x0, job.seg_w,
                                       job.qp, job.first_slice != 0,
                                       job.slice_addr, job.addr_bits,
-                                      o.bytes, fc_);
+                                      o.bytes, fc_, job.slice_type,
+                                      job.poc_lsb);
           } else {
             hevc::assemble_hevc_slice_nal(
                 h_out_[par] + (size_t)j * out_stride_,
                 h_counts_[par][j * 3], h_counts_[par][j * 3 + 1],
                 h_counts_[par][j * 3 + 2], job.first_slice != 0,
-                job.slice_addr, job.addr_bits, job.qp, o.bytes);
+                job.slice_addr, job.addr_bits, job.qp, o.bytes,
+                job.slice_type, job.poc_lsb);
           }
         }
       });
@@ -227,7 +274,7 @@ class HipHevcPipeline : public EncodePipeline {
       s.y = o.y0;
       s.width = w_;
       s.height = o.vis_h;
-      s.is_keyframe = true;
+      s.is_keyframe = o.idr;
       emit(s);
     }
   }
@@ -295,6 +342,7 @@ class HipHevcPipeline : public EncodePipeline {
   void alloc_for(int w, int h) {
     prev_ = Pending{};          // in-flight frame is gone with its buffers
     parity_ = 0;
+    sstate_.clear();            // new planes hold no reference picture
     stream_.sync();
     rows_stream_.sync();
     arena_.release();
@@ -336,6 +384,15 @@ class HipHevcPipeline : public EncodePipeline {
     // tests/test_hevc_recon_host.py): uniform noise 500, saturated 2x2
     // colour checker 247, 1-pixel 0/255 checkerboard 169. The stride is
     // at least 2x the largest figure, which the host test asserts.
+    // P slices stay inside it. A skip or merge CTU codes the same three
+    // TBs with the same level clamp and a smaller rounding offset
+    // (85 < 171), so no more levels than an intra CTU, behind a prefix of
+    // at most 4 bins (cu_skip, pred_mode, part_mode, merge). An intra CTU
+    // of a P slice is the larger case: the whole intra syntax plus
+    // cu_skip_flag and pred_mode_flag, under initType-1 contexts; on
+    // uniform noise, where every P CTU ends up intra, that measured +0.4
+    // to +1.0% bytes over the I slices (profiles/NOTES.md), which the 2x
+    // margin over the measured 500 bytes per CTU covers.
     const int per = (ctbw_ + spr - 1) / spr;
     out_stride_ = per * kBytesPerCtu;
     // fullcolor codes 768 coefficients per CTU, so that argument does not
@@ -372,6 +429,8 @@ class HipHevcPipeline : public EncodePipeline {
   bool cpu_entropy_ = false;
   bool timing_ = false;
   const bool fc_;         // video_fullcolor: Main 4:4:4 instead of 4:2:0
+  const bool inter_;      // hevc_inter && !fc_: P stripes after each IDR
+  std::vector<StripeState> sstate_;   // per ctx.stripes index
   int stripe_h_ = 64;
   int depth_ = 1;         // 1 = sync (latency mode), 2 = pipelined
   int parity_ = 0;

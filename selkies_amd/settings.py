@@ -184,6 +184,12 @@ SETTING_DEFINITIONS: list[SettingDef] = [
                "4:4:4 chroma (I444) instead of 4:2:0: JPEG, H.264 (Hi444) "
                "and HEVC (Main 4:4:4).",
                client=True),
+    SettingDef("hevc_inter", bool, False,
+               "HEVC (hevcenc-striped, 4:2:0 only): after a stripe's key "
+               "picture send zero-motion P pictures (skip / merge + "
+               "residual / intra CTUs) against its previous picture "
+               "instead of all-intra stripes. Ignored with "
+               "video_fullcolor."),
     SettingDef("video_pipeline_depth", int, 1,
                "Encoder frame pipelining depth: 1 = synchronous (lowest "
                "interactive latency), 2 = one frame in flight (throughput "

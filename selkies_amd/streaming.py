@@ -180,6 +180,7 @@ class StreamingService:
         cs.vbv_multiplier = s.video_vbv_multiplier
         cs.keyframe_interval_s = s.keyframe_interval_s
         cs.video_fullcolor = s.video_fullcolor
+        cs.hevc_inter = s.hevc_inter
         cs.video_deblock = s.video_deblock
         cs.video_fullframe = s.video_fullframe
         cs.capture_scale = s.capture_scale
@@ -689,7 +690,8 @@ class StreamingService:
             await state.ws.send_str(reply)
 
     # ---- settings application ----------------------------------------------
-    STRUCTURAL = {"encoder", "resolution", "video_fullcolor", "use_cpu",
+    STRUCTURAL = {"encoder", "resolution", "video_fullcolor", "hevc_inter",
+                  "use_cpu",
                   "capture_scale",
                   "video_fullframe"}
 

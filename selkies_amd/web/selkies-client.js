@@ -87,6 +87,18 @@ function hevcCodecString(payload) {
 }
 /* hevcCodecString:end */
 
+/* hevcStripeCodec:begin (pure; tests/hevc_p evaluates this block in node,
+ * after the hevcCodecString block it calls) */
+/* Codec string for an HEVC stripe. Key stripes start with the VPS and are
+ * read by hevcCodecString. Delta stripes (TRAIL_R slices only, no VPS) must
+ * not be: they return the codec the row already decodes with (rowCodec),
+ * or null when the row was never configured, which drops the delta. */
+function hevcStripeCodec(key, payload, rowCodec) {
+  if (key) return hevcCodecString(payload);
+  return rowCodec || null;
+}
+/* hevcStripeCodec:end */
+
 const h264Rows = new Map();   // y -> H264Row
 let jpegDrawQueue = Promise.resolve();
 
@@ -107,11 +119,15 @@ function onBinary(buf) {
     const h = (d[8] << 8) | d[9];
     ensureCanvas(w, y + h);
     // 0x06 = HEVC, Main or Main 4:4:4 (video_fullcolor); per-row decoders.
-    // Delta stripes never occur for HEVC (all-intra), so every stripe
-    // carries its VPS and names its own profile.
-    const codec = tag === 0x06 ? hevcCodecString(d.subarray(10))
-                               : "avc1.42e028";
-    let row = h264Rows.get(y);
+    // A key stripe carries its VPS and names its own profile; a delta
+    // stripe (hevc_inter P picture) has no parameter sets and keeps the
+    // codec its row was configured with.
+    const prev = h264Rows.get(y);
+    const codec = tag === 0x06
+        ? hevcStripeCodec(key, d.subarray(10), prev ? prev.codec : null)
+        : "avc1.42e028";
+    if (codec === null) { requestIdr(); return; }   // delta before any key
+    let row = prev;
     if (!row || row.codec !== codec) {
       row = new H264Row(y, codec); h264Rows.set(y, row);
     }
